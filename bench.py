@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising steps/sec of the latent-video hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sample|train] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu] [--no-breakdown] ...]
 
 Workload (BASELINE.json configs[1]): latent U-Net num_channels=64, num_res_blocks=1, max_frames=20,
 batch 2, 1000-step DDPM ancestral sampling (p_sample loop) on synthetic 4x16x16 latents.  A "step" is one
@@ -15,14 +15,22 @@ before anything here touches the GPU) and passes their JSON line through.  Sampl
 parallelises sampling over videos, video_sample.py:192-200): every rank samples its own videos - weak scaling,
 `value` = N*K / max-over-ranks time.  The part of the path that does exchange data - training at BASELINE.json
 configs[2], batch sharded over the ranks, bucketed gradient all-reduce overlapped with the backward pass - is timed in
-the same run and reported at top level for N > 1 (`train_videos_per_s`, `allreduce_bytes_per_step`,
+the same run under `--full` and reported at top level for N > 1 (`train_videos_per_s`, `allreduce_bytes_per_step`,
 `exposed_allreduce_ms_per_step`, `collective_world_size`, `collective_backend`) and under `train` in full.
 On a box with fewer than N GPUs the ranks share the cards and the collective backend falls back to gloo (a rehearsal
 of the plumbing, labelled as such in the line).
 
-One JSON line on stdout (rank 0) with `roofline` (dominant kernel = the implicit-GEMM conv, live HIP-event timing, every
-tile-shape instance listed) and `cpu_baseline` (the CPU oracle restatement of the same step: all cores, one thread, and a
-training step; bounded samples).
+A plain run does only what the headline needs: set up, warm up, time exactly K steps (one region; `--min-seconds S`
+repeats K-step regions until S seconds are timed), and print one JSON line on stdout (rank 0) with `value` and
+`ms_per_step`.  `--dump-outputs DIR` then also writes what the timed path returned after its last step - the
+`sample` and `pred_xstart` arrays of GraphSampler.run, float32 - as DIR/<name>.npy (rank 0); weights, inputs and noise
+are seeded, so the same arguments give the same inputs in every run.
+
+`--full` adds everything else to the same line: the public-API chain (`public_api`), the training leg and the exchange
+probe (`train`, and at N > 1 the top-level keys named above), the long-video and pixel-space legs, `roofline` (dominant
+kernel = the implicit-GEMM conv, live HIP-event timing, every tile-shape instance listed), `breakdown`, `hbm_phases`,
+`code_stamp` and `cpu_baseline` (the CPU oracle restatement of the same step: all cores, one thread, and a training step;
+bounded samples).  The options that size or skip those legs (`--no-cpu`, `--train-steps`, ...) act under `--full` only.
 """
 import argparse
 import json
@@ -795,6 +803,17 @@ def timed_sampling(sampler, steps, world, dev, min_seconds, n_t):
             return times
 
 
+def dump_outputs(path, arrays, limit_bytes=64 << 20):
+    """Write each device tensor of `arrays` as `path/<name>.npy` in float32 (64 MB at most in all)."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > limit_bytes:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {limit_bytes})")
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     # tile shapes measured once on an MI355X and committed (loaded read-only): the same kernels run in every bench /
     # profile pass
@@ -803,7 +822,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=900)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="repeat the K-step timed region until this much is timed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step timed region until this much is timed (default: one region of exactly K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the sample and pred_xstart of the last one as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the public-API chain, the training / long-video / pixel legs, the kernel breakdown and "
+                         "roofline, the HBM phases and the CPU baselines (the options below act under --full only)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
     ap.add_argument("--no-breakdown", action="store_true")
     ap.add_argument("--train-steps", type=int, default=30, help="timed optimizer steps of the training leg (0 = skip)")
@@ -871,6 +896,9 @@ def main():
     i = max(i - k, 0)
     times = timed_sampling(sampler, args.steps, world, dev, args.min_seconds, diffusion.num_timesteps)
     regions = len(times)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path (GraphSampler.run) receives after its last step; begin() below overwrites it
+        dump_outputs(args.dump_outputs, {"sample": sampler.plan.x_in, "pred_xstart": sampler.pred})
     # Work that the sampler does once per CHAIN instead of once per step (the R tables: everything that depends on the
     # timestep and this chain's frame indices, GraphSampler.begin) is charged to every timed step at 1/chain-length of
     # its cost.  What is done once per set of WEIGHTS (graph capture, launch tuning, the FiLM tables) is reported as
@@ -880,28 +908,30 @@ def main():
     # charged to every timed step at 1/chain-length; the window's refills run in-stream inside the timed regions
     sampler.begin(th.randn(*shape, device=dev), inputs)
     table_ms = float(sampler.table_build_ms)
-    chain_table_ms = float(sampler.chain_table_ms())       # (for the record: every R block of a chain once)
     per_step_s = table_ms * 1e-3 / diffusion.num_timesteps
     el_steps = sum(times)
     el = el_steps + per_step_s * args.steps * regions
     finite = bool(th.isfinite(sampler.plan.x_in).all().item())
     tables_info = (sampler.plan.time_table_bytes, sampler.plan.time_table_fallback)   # fallback: why the per-step plan runs
-    # ---- the metric's own definition: one whole chain through the public p_sample_loop (reference
-    # gaussian_diffusion.py:403-522: noise draw, per-chain tables, 1000 x p_sample, final clone), wall clock
-    th.manual_seed(4321 + rank)
-    diffusion.p_sample_loop(model, shape, model_kwargs=inputs, return_decoded=False)        # (warm: same sampler object)
-    th.cuda.synchronize()
-    walls = []
-    for _ in range(2):
-        t0 = time.perf_counter()
-        pub, _ = diffusion.p_sample_loop(model, shape, model_kwargs=inputs, return_decoded=False)
+    public_api = None
+    if args.full:
+        chain_table_ms = float(sampler.chain_table_ms())   # (for the record: every R block of a chain once)
+        # ---- the metric's own definition: one whole chain through the public p_sample_loop (reference
+        # gaussian_diffusion.py:403-522: noise draw, per-chain tables, 1000 x p_sample, final clone), wall clock
+        th.manual_seed(4321 + rank)
+        diffusion.p_sample_loop(model, shape, model_kwargs=inputs, return_decoded=False)    # (warm: same sampler object)
         th.cuda.synchronize()
-        walls.append(time.perf_counter() - t0)
-    public_wall = min(walls)
-    public_api = {"p_sample_loop_wall_ms": round(1000.0 * public_wall, 2), "chain_steps": diffusion.num_timesteps,
-                  "steps_per_s_public_api": round(diffusion.num_timesteps / public_wall, 2),
-                  "finite": bool(th.isfinite(pub).all().item()),
-                  "note": "diffusion.p_sample_loop(model, shape, model_kwargs=..., return_decoded=False), best of 2 warm chains"}
+        walls = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            pub, _ = diffusion.p_sample_loop(model, shape, model_kwargs=inputs, return_decoded=False)
+            th.cuda.synchronize()
+            walls.append(time.perf_counter() - t0)
+        public_wall = min(walls)
+        public_api = {"p_sample_loop_wall_ms": round(1000.0 * public_wall, 2), "chain_steps": diffusion.num_timesteps,
+                      "steps_per_s_public_api": round(diffusion.num_timesteps / public_wall, 2),
+                      "finite": bool(th.isfinite(pub).all().item()),
+                      "note": "diffusion.p_sample_loop(model, shape, model_kwargs=..., return_decoded=False), best of 2 warm chains"}
     # persistent level chains of the TIMED plan, and that none of their waits timed out (a timed-out chain leaves garbage in
     # the samples and the sampler falls back to one launch per stage: neither may end up in the line)
     pl_ = sampler.plan
@@ -914,7 +944,7 @@ def main():
     if chains_rec["timed_out"] or chains_rec["fell_back"]:
         raise SystemExit("bench.py: a persistent level chain timed out (LFVDM_CHAIN_TIMEOUT_S) during the timed run")
     train = None
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         del sampler
         diffusion._samplers.clear()
         th.cuda.empty_cache()
@@ -930,15 +960,11 @@ def main():
         "ms_per_step": round(1000.0 * el / total_steps, 4), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "timed_regions": regions, "timed_seconds": round(el_steps, 4),
-        "p_sample_loop_wall_ms": public_api["p_sample_loop_wall_ms"],
-        "steps_per_s_public_api": public_api["steps_per_s_public_api"],
-        "public_api": public_api,
         "per_chain_setup": {"begin_table_build_ms": round(table_ms, 3), "table_build_ms": round(table_ms, 3), "first_chain_table_build_ms": round(cold_setup_ms, 3),
                             "chain_steps": diffusion.num_timesteps,
                             "charged_ms_per_step": round(1000.0 * per_step_s, 5),
                             "timestep_table_bytes": int(tables_info[0]), "fallback": tables_info[1],
                             "r_table_ring_steps": int(getattr(sampler.plan, "time_ring", 0)),
-                            "r_table_build_ms_per_chain_in_stream": round(chain_table_ms, 3),
                             "note": "value and ms_per_step include the amortised share of begin(); the rolling window's refills "
                                     "(r_table_build_ms_per_chain_in_stream) run inside the timed regions; timed_seconds is the raw time"},
         "region_ms_per_step_min_max": [round(1000.0 * min(times) / args.steps, 4), round(1000.0 * max(times) / args.steps, 4)],
@@ -949,6 +975,11 @@ def main():
                    "steps_per_graph_launch": int(getattr(sampler, "K", 1)),
                    "gpus_requested": args.gpus},
     }
+    if args.full:
+        out["p_sample_loop_wall_ms"] = public_api["p_sample_loop_wall_ms"]
+        out["steps_per_s_public_api"] = public_api["steps_per_s_public_api"]
+        out["public_api"] = public_api
+        out["per_chain_setup"]["r_table_build_ms_per_chain_in_stream"] = round(chain_table_ms, 3)
     out["level_chains"] = chains_rec
     # ---- the collective, self-checked: what the launcher asked for is what the process group is
     rehearsal = world > 1 and backend != "nccl"
@@ -962,8 +993,9 @@ def main():
     out["self_check"] = checks
     if not all(checks.values()):
         raise SystemExit(f"bench.py self-check failed: {checks} (WORLD_SIZE={world}, backend={backend}, devices={n_dev})")
-    public_api["agrees_with_value_within_3pct"] = abs(public_api["steps_per_s_public_api"] * world / out["value"] - 1.0) <= 0.03
-    out["code_stamp"] = running_code_stamp()
+    if args.full:
+        public_api["agrees_with_value_within_3pct"] = abs(public_api["steps_per_s_public_api"] * world / out["value"] - 1.0) <= 0.03
+        out["code_stamp"] = running_code_stamp()
     if train is not None and world == 1 and rank == 0 and args.machinery_steps > 0:
         # one GPU can report what the exchange machinery costs with today's code (before any byte crosses xGMI)
         probe = exchange_machinery_probe(dev, args.machinery_steps)
@@ -992,7 +1024,7 @@ def main():
                                                                     "buckets_started_inside_the_backward", "overlap_probe",
                                                                     "machinery_ms_per_step", "rccl_world1_copy_ms_per_step",
                                                                     "machinery_minus_rccl_copy_ms_per_step")}
-    if rank == 0:
+    if rank == 0 and args.full:
         # the single-GPU legs (configs[3], configs[4]) and the CPU baselines belong to the N = 1 line only
         if args.long_video_windows > 0 and world == 1:
             out["long_video"] = bench_long_video(dev, args.long_video_windows)
@@ -1092,6 +1124,7 @@ def main():
             out["cpu_baseline"]["cfgC_sample"] = cpu_baseline_sample(mc, inputs, B, T, cores, 6.0,
                                                                      what="the configs[2] network (ch128, batch 2, 20 frames)")
             del ma, mc
+    if rank == 0:
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if dist.is_initialized():            # (the training leg initialises a world-1 group too)

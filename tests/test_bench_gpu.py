@@ -30,7 +30,8 @@ def _run(argv, timeout=900):
 
 
 def test_two_rank_rehearsal_line_is_self_checking():
-    d = _run(["--gpus", "2", "--steps", "20", "--train-steps", "4", "--no-cpu", "--pixel-steps", "0", "--long-video-windows", "0"])
+    d = _run(["--gpus", "2", "--steps", "20", "--min-seconds", "0.5", "--full", "--train-steps", "4", "--no-cpu", "--pixel-steps", "0",
+              "--long-video-windows", "0"])
     for k in CONTRACT + MULTI:
         assert k in d, k
     assert d["n_gpus"] == 2 and d["collective_world_size"] == 2 and d["scaling"] == "weak" and d["steps"] == 20
@@ -48,8 +49,8 @@ def test_two_rank_rehearsal_line_is_self_checking():
 
 
 def test_one_rank_line_has_the_same_schema():
-    d = _run(["--steps", "50", "--train-steps", "6", "--machinery-steps", "6", "--no-cpu", "--pixel-steps", "0",
-              "--long-video-windows", "0", "--no-breakdown"])
+    d = _run(["--steps", "50", "--min-seconds", "0.5", "--full", "--train-steps", "6", "--machinery-steps", "6", "--no-cpu",
+              "--pixel-steps", "0", "--long-video-windows", "0", "--no-breakdown"])
     for k in CONTRACT + MULTI:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["collective_world_size"] == 1 and d["allreduce_bytes_per_step"] == 0
@@ -71,6 +72,29 @@ def test_one_rank_line_has_the_same_schema():
         assert hp[k]["bytes"] > 0 and hp[k]["us"] > 0 and 0 < hp[k]["frac"] < 1, (k, hp[k])
     assert hp["adamw_ema"]["frac"] > 0.4, hp["adamw_ema"]
     assert d["code_stamp"]["abi"] > 0
+
+
+def test_plain_line_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: one timed region of exactly --steps steps, the headline keys and none of the extra legs; with
+    --dump-outputs the sample and pred_xstart after the last timed step, the same in two runs with the same arguments."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        d = _run(["--steps", "24", "--warmup", "5", "--dump-outputs", str(out_dir)])
+        for k in CONTRACT:
+            assert k in d, k
+        assert d["steps"] == 24 and d["warmup"] == 5 and d["timed_regions"] == 1 and d["n_gpus"] == 1
+        assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] / 1000.0 - 1.0) < 1e-3, d
+        for k in ("public_api", "train", "long_video", "pixel", "roofline", "breakdown", "hbm_phases", "cpu_baseline"):
+            assert k not in d, k
+        arrays = {n: np.load(out_dir / f"{n}.npy") for n in ("sample", "pred_xstart")}
+        for n, a in arrays.items():
+            assert a.dtype == np.float32 and a.shape == (2, 20, 4, 16, 16) and np.isfinite(a).all(), n
+        dumps.append(arrays)
+    # (launch tuning may pick another tile shape in the second run; x0-hat divides by sqrt(alpha_bar) ~ 0.01 near t = 999)
+    np.testing.assert_allclose(dumps[1]["sample"], dumps[0]["sample"], rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(dumps[1]["pred_xstart"], dumps[0]["pred_xstart"], rtol=1e-4, atol=1e-3)
 
 
 def test_pixel_training_leg_runs_the_published_recipe():

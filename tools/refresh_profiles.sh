@@ -61,8 +61,8 @@ rm -rf $OUT/pxp/*trace*
 echo "pixel train profile done"
 fi
 if want bench; then
-step 300 python3 $ROOT/bench.py --steps 100 --warmup 20 --train-steps 0 --pixel-steps 0 --long-video-windows 4 --no-cpu --no-breakdown > $OUT/bpwarm.log 2>&1   # (tunes what the table lacks)
-step 300 rocprofv3 --kernel-trace --stats -d $OUT/bp -o bp --output-format csv -- python3 $ROOT/bench.py --steps 300 --warmup 20 --train-steps 0 --pixel-steps 0 --long-video-windows 0 --no-cpu > $OUT/bp.log 2>&1
+step 300 python3 $ROOT/bench.py --full --min-seconds 0.5 --steps 100 --warmup 20 --train-steps 0 --pixel-steps 0 --long-video-windows 4 --no-cpu --no-breakdown > $OUT/bpwarm.log 2>&1   # (tunes what the table lacks)
+step 300 rocprofv3 --kernel-trace --stats -d $OUT/bp -o bp --output-format csv -- python3 $ROOT/bench.py --full --min-seconds 0.5 --steps 300 --warmup 20 --train-steps 0 --pixel-steps 0 --long-video-windows 0 --no-cpu > $OUT/bp.log 2>&1
 cp $OUT/bp/bp_kernel_stats.csv $OUT/bench_kernel_stats.csv
 stamp $OUT/bench_kernel_stats.csv bench_kernel_stats.csv
 echo "bench profile done"
@@ -80,7 +80,7 @@ fi
 if want line; then
 # 4b. the default bench line LAST among the measurements it quotes: train / pixel-train family splits and PMC traffic are
 #     read from profiles/${ROUND}_*, which must be THIS run's files (stamped with the running code)
-step 500 python3 $ROOT/bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+step 500 python3 $ROOT/bench.py --full --min-seconds 0.5 > $OUT/bench_line.json 2> $OUT/bench.err
 echo "bench done"
 fi
 # 5. in-kernel phase table of the implicit-GEMM launches (diagnostic build with -DLFVDM_STAMP, if present)
@@ -99,7 +99,7 @@ echo "parity deviations done"
 fi
 if want long; then
 # 7. the whole 1000-frame hierarchy-2 video (BASELINE.json configs[3] at full size: 97 windows x 250 steps)
-step 400 python3 $ROOT/bench.py --steps 50 --warmup 10 --train-steps 0 --pixel-steps 0 --no-cpu --long-video-windows 97 > $OUT/long_video_line.json 2> $OUT/long_video.err
+step 400 python3 $ROOT/bench.py --full --min-seconds 0.5 --steps 50 --warmup 10 --train-steps 0 --pixel-steps 0 --no-cpu --long-video-windows 97 > $OUT/long_video_line.json 2> $OUT/long_video.err
 echo "long video done"
 fi
 if want localbench; then
