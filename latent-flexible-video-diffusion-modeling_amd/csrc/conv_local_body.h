@@ -402,16 +402,22 @@ __device__ __forceinline__ bool conv_local_body(const lfvdm_conv_args& p, int fr
             const int gw = p.gn_gw ? p.gn_gw : p.Cout >> 5, gld = p.gn_ld ? p.gn_ld : p.Cout;
             const bool two = gw == 2;
             const float inv = 1.0f / (float)(P * gw);
-            // (the 16 rows of a tile are one DPP row: quad_perm xor 1 / xor 2, then row rotations by 4 and 8 - every lane
-            // ends with its sample's total; a ds_bpermute butterfly costs an LDS round trip per step)
+            // (the 16 rows of a tile are one DPP row, a sample the aligned group of P lanes in it: quad_perm xor 1 / xor 2
+            // sum a quad; P == 8 (two samples per tile) adds the other quad of its half-row by row_half_mirror; P == 16 adds
+            // the three other quads by row rotations by 4 and 8 - a rotation by 4 alone would cross into the other sample at
+            // P == 8.  Every lane ends with its sample's total.  P is run-time and workgroup-uniform: the branch is scalar.
+            // A ds_bpermute butterfly costs an LDS round trip per step)
             auto dpp = [](float v, auto ctrl) {
                 return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), decltype(ctrl)::value, 0xF, 0xF, true));
             };
             auto rows_sum = [&](float v) {
                 if (P >= 2) v += dpp(v, std::integral_constant<int, 0xB1>{});         // quad_perm [1,0,3,2]
                 if (P >= 4) v += dpp(v, std::integral_constant<int, 0x4E>{});         // quad_perm [2,3,0,1]
-                if (P >= 8) v += dpp(v, std::integral_constant<int, 0x124>{});        // row_ror:4
-                if (P >= 16) v += dpp(v, std::integral_constant<int, 0x128>{});       // row_ror:8
+                if (P == 8) v += dpp(v, std::integral_constant<int, 0x141>{});        // row_half_mirror
+                if (P >= 16) {
+                    v += dpp(v, std::integral_constant<int, 0x124>{});                // row_ror:4
+                    v += dpp(v, std::integral_constant<int, 0x128>{});                // row_ror:8
+                }
                 return v;
             };
             auto unit_sum = [&](float& a, float& b) {

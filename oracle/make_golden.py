@@ -396,6 +396,89 @@ def gen_sampler_cfgB():
     print("[sampler cfgB] ok", np.stack(traj).shape)
 
 
+# Non-square latents and the reference's own 32x32 latent shape: name -> (cfg kwargs, B, T, H, W, n_pad, sampler subsample)
+NONSQUARE = {
+    "cfgB_16x32": (CONFIGS["cfgB"][0], 2, 20, 16, 32, 3, (2, 4)),
+    "cfgB_32x16": (CONFIGS["cfgB"][0], 2, 20, 32, 16, 3, None),
+    # levels 8x24 / 4x12 / 2x6 / 1x3: no level's pixel count is a power of two
+    "cfgB_8x24": (CONFIGS["cfgB"][0], 2, 20, 8, 24, 3, None),
+    # the reference's defaults for 4x32x32 latents (carla_no_traffic_2x_encoded, video_datasets.py:34; script_util.py:16-20,
+    # 108-115): ch128, num_res_blocks=2, channel_mult (1,2,2,2), attention "16,8" = ds 2, 4, 4 heads
+    "carla32": (dict(model_channels=128, num_res_blocks=2, channel_mult=(1, 2, 2, 2), attention_resolutions=(2, 4), num_heads=4),
+                2, 20, 32, 32, 3, (4, 4)),
+}
+FULL_OUTPUT_FLOATS = 90_000         # outputs up to this size are stored whole (~350 KB), larger ones as a stride-2 subsample
+
+
+def _compact(x64, stride):
+    """fp32 subsample [..., ::sy, ::sx] plus per-(frame, channel) sums and L2 norms of the whole map, in fp64"""
+    sy, sx = stride
+    return dict(sub=x64[..., ::sy, ::sx].float().numpy(), frame_sum=x64.sum(dim=(-1, -2)).numpy(),
+                frame_norm=x64.pow(2).sum(dim=(-1, -2)).sqrt().numpy(), absmax=np.float64(x64.abs().max()),
+                stride=np.array(stride, dtype=np.int64))
+
+
+def gen_forward_nonsquare(names=("cfgB_16x32", "cfgB_32x16", "cfgB_8x24", "carla32")):
+    """Forward fixtures in FLOAT64, so that they are the truth and not one fp32 rounding of it.  The reference itself cannot
+    run in fp64: it casts to fp32 in GroupNorm32 (nn.py:19), the timestep embedding (nn.py:117-119), the attention softmax
+    (rpe.py:163) and the torso (unet.py:453).  So the stored values are the oracle's fp64 forward, and the reference's fp32
+    forward is checked against them on the spot, at the fp32 bound of gen_forward_cfgE_T20.  Small outputs are stored whole,
+    larger ones compactly (_compact)."""
+    for name in names:
+        kw, B, T, H, W, n_pad, _ = NONSQUARE[name]
+        cfg = uo.make_cfg(**kw)
+        model, sd = build_reference_model(cfg)
+        inp = recipe.make_inputs(name, B, T, cfg["in_channels"], H, W, n_pad=n_pad)
+        ti = tt(inp)
+        f64 = lambda t: t.double() if t.is_floating_point() else t      # noqa: E731
+        with torch.no_grad():
+            ref, _ = model(ti["x"], x0=ti["x0"], timesteps=ti["t"].float(), frame_indices=ti["frame_indices"],
+                           obs_mask=ti["obs_mask"], latent_mask=ti["latent_mask"])
+            sd64 = {k: v.double() for k, v in sd.items()}
+            t64, _ = uo.unet_forward(sd64, cfg, f64(ti["x"]), f64(ti["x0"]), ti["t"].double(), ti["frame_indices"],
+                                     f64(ti["obs_mask"]), f64(ti["latent_mask"]))
+        assert t64.dtype == torch.float64 and t64.shape == (B, T, cfg["out_channels"], H, W)
+        d = maxdiff(ref.double(), t64)
+        print(f"[forward {name}] {H}x{W} out rms {float(t64.pow(2).mean().sqrt()):.4f}  fp32 reference vs fp64 oracle max|d| {d:.3e}")
+        assert d < 2e-4
+        meta = dict(frame_indices=inp["frame_indices"], n_params=np.int64(sum(v.numel() for v in sd.values())),
+                    x_sum=np.float64(inp["x"].astype(np.float64).sum()), ref_dev=np.float64(d))
+        if t64.numel() <= FULL_OUTPUT_FLOATS:
+            body = dict(out=t64.float().numpy(), absmax=np.float64(t64.abs().max()))
+        else:
+            body = _compact(t64, (2, 2))
+        np.savez_compressed(os.path.join(OUT, f"forward_{name}.npz"), **body, **meta)
+
+
+def gen_sampler_nonsquare(names=("cfgB_16x32", "carla32")):
+    """Three reference p_sample steps from t = 999 with recipe noise, as gen_sampler_cfgB (fp32), stored compactly."""
+    for name in names:
+        kw, B, T, H, W, n_pad, stride = NONSQUARE[name]
+        cfg = uo.make_cfg(**kw)
+        model, sd = build_reference_model(cfg)
+        inp = tt(recipe.make_inputs(name, B, T, cfg["in_channels"], H, W, n_pad=n_pad))
+        shape = inp["x"].shape
+        pixel = {"diffusion_space": "pixel", "pre_encoded": False, "pre_encoded_stats_dict": None}
+        diff = rsu.create_gaussian_diffusion(steps=1000, timestep_respacing="", rescale_timesteps=True, rescale_learned_sigmas=True,
+                                             diffusion_space_kwargs=dict(pixel))
+        mk = dict(frame_indices=inp["frame_indices"], obs_mask=inp["obs_mask"], latent_mask=inp["latent_mask"], x0=inp["x0"])
+        noise = [torch.from_numpy(recipe.gaussianish(f"sampler_{name}/noise{i}", inp["x"].numel()).reshape(shape).astype(np.float32))
+                 for i in range(3)]
+        real_randn_like = torch.randn_like
+        x, traj = inp["x"].clone(), []
+        for j, i in enumerate(range(999, 996, -1)):
+            torch.randn_like = lambda x_, _n=noise[j]: _n
+            try:
+                with torch.no_grad():
+                    x = diff.p_sample(model, x, torch.tensor([i] * B), clip_denoised=True, model_kwargs=mk)["sample"]
+            finally:
+                torch.randn_like = real_randn_like
+            traj.append(x.double())
+        body = _compact(torch.stack(traj), stride)
+        np.savez_compressed(os.path.join(OUT, f"sampler_{name}.npz"), **body)
+        print(f"[sampler {name}] ok", tuple(body["sub"].shape))
+
+
 def gen_sampler_cfgD_window():
     """The long-video path (BASELINE.json configs[3]): batch 1, the configs[1] network, 250-step respacing, windows of the
     reference's hierarchy-2 schedule for T=1000 / 36 observed / K=20 / step 10 (tests/golden/schemes.json, itself generated
@@ -540,6 +623,10 @@ if __name__ == "__main__":
         gen_backward(names=["micro_px", "cfgE_T2"])
         gen_sampler_cfgD_window()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "nonsquare":      # non-square latents and the 32x32 reference defaults
+        gen_forward_nonsquare()
+        gen_sampler_nonsquare()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "cfgD_window":
         gen_sampler_cfgD_window()
         sys.exit(0)
@@ -558,4 +645,6 @@ if __name__ == "__main__":
     gen_train_step_cfgC()
     gen_forward_cfgE_T20()
     gen_sampler_cfgD_window()
+    gen_forward_nonsquare()
+    gen_sampler_nonsquare()
     print("golden vectors written to", OUT)

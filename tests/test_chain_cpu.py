@@ -185,10 +185,12 @@ def local_item_deps(st, deps, item):
 
 
 def local_stage(src, out, Cin, Cout, N, Hs, Ho, rt, gn_out=0, skip_raw=0, res=0, stride=1, up=0, s2=(0, 0, 0, 0), ksize=3):
+    """Hs / Ho: an int (square map) or (rows, columns)"""
+    (Hs, Ws), (Ho, Wo) = [(h, h) if isinstance(h, int) else h for h in (Hs, Ho)]
     st = conv_stage(src, out, Cin, Cout, N, Hs, 0, gn_out=gn_out, skip_raw=skip_raw, res=res, ksize=ksize)
     st.kind, st.cfg = nat.CHAIN_LOCAL, rt
     a = st.conv
-    a.Ho, a.Wo, a.stride, a.up = Ho, Ho, stride, up
+    a.Ws, a.Ho, a.Wo, a.stride, a.up = Ws, Ho, Wo, stride, up
     if s2[0]:
         a.s2src0, a.s2C0, a.s2src1, a.s2C1, a.W2, a.bias2 = s2[0], s2[1], s2[2] or None, s2[3], 0x50, 0x60
     return st
@@ -262,6 +264,60 @@ def test_sample_local_stage_acceptance():
     for item in range(st[2].n_items):
         rg = item // 8
         assert local_item_deps(st[2], deps, item) == [[st[1].flag_base + w * 5 + rg // 2] for w in range(4)]
+
+
+@pytest.mark.parametrize("rt", [1, 2])
+def test_sample_local_stage_accepts_every_map_of_at_most_16_pixels_whose_size_is_a_power_of_two(rt):
+    """P = Ho*Wo must divide a 16-row tile (a sample's rows are an aligned lane group of a DPP row): square or not, and with
+    the operand forms that reach those maps (stride 2, nearest 2x, a 1x1 skip segment over a concat, the concat-half
+    normalisation).  P = 3, 6, 12, 32 straddle tiles: refused - the caller keeps the tile kernel."""
+    L = nat.lib()
+    ok = lambda st: L.lfvdm_chain_local_ok(C.byref(st.conv), rt) == 0       # noqa: E731
+    for hw in [(2, 4), (4, 2), (8, 1), (1, 8), (1, 2), (2, 1), (1, 1), (4, 1), (1, 4), (2, 2), (4, 4), (2, 8), (8, 2), (16, 1)]:
+        assert ok(local_stage(0x1000, 0x2000, 128, 128, 40, hw, hw, rt, gn_out=0x3000)), hw
+        assert ok(local_stage(0x1000, 0x2000, 128, 128, 40, hw, hw, rt, gn_out=0x3000, res=0x4000, ksize=1)), hw
+    assert ok(local_stage(0x1000, 0x2000, 128, 128, 40, (4, 8), (2, 4), rt, gn_out=0x3000, stride=2))
+    assert ok(local_stage(0x1000, 0x2000, 128, 128, 40, (2, 4), (1, 2), rt, gn_out=0x3000, stride=2))
+    assert ok(local_stage(0x1000, 0x2000, 128, 128, 40, (1, 2), (2, 4), rt, gn_out=0x3000, up=1))
+    assert ok(local_stage(0x1000, 0x2000, 128, 128, 40, (2, 4), (2, 4), rt, gn_out=0x3000, s2=(0x5000, 128, 0x6000, 64)))
+    half = local_stage(0x1000, 0x2000, 128, 128, 40, (4, 2), (4, 2), rt, gn_out=0x3000)
+    half.conv.gn_gw, half.conv.gn_ld = 8, 256
+    assert ok(half)
+    for hw in [(1, 3), (3, 1), (2, 3), (3, 2), (1, 6), (3, 4), (4, 3), (2, 6), (1, 12), (4, 8), (8, 4), (2, 16), (1, 32)]:
+        assert not ok(local_stage(0x1000, 0x2000, 128, 128, 40, hw, hw, rt, gn_out=0x3000)), hw
+        assert not ok(local_stage(0x1000, 0x2000, 128, 128, 40, hw, hw, rt)), hw
+    assert not ok(local_stage(0x1000, 0x2000, 128, 128, 40, (4, 8), (2, 3), rt, stride=2))     # inconsistent geometry
+    assert not ok(local_stage(0x1000, 0x2000, 128, 128, 40, (2, 4), (2, 8), rt, up=1))
+    assert not ok(local_stage(0x1000, 0x2000, 128, 128, 40, (6, 10), (3, 5), rt, stride=2))    # P = 15
+
+
+def test_sample_local_stages_on_2x4_maps_wait_for_whole_samples():
+    """The bottom levels of a 16x32 latent: a stride-2 4x8 -> 2x4 stage (P = 8: two samples per 16-row tile), a 2x4 stage
+    of two row tiles per item, a stride-2 2x4 -> 1x2 stage (P = 2: eight samples per tile) and a nearest-2x 1x2 -> 2x4 stage.
+    Items = row groups x filter slices; an item's wave w waits for the producer's 16-row tiles that hold ALL source rows of
+    its samples (a whole number of samples: 2, 4, 8 samples of 8, 32, 64 rows), channel slices 2w, 2w+1."""
+    N, Ch = 40, 128
+    NS = Ch // 16
+    X, R0, A0, R1, A1, R2, R3 = 0x100000, 0x200000, 0x300000, 0x400000, 0x500000, 0x600000, 0x700000
+    s0 = local_stage(X, R0, Ch, Ch, N, (4, 8), (2, 4), 1, gn_out=A0, stride=2)      # M = 320: 20 tiles of 2 samples
+    s1 = local_stage(A0, R1, Ch, Ch, N, (2, 4), (2, 4), 2, gn_out=A1)               # 10 items of 4 samples
+    s2 = local_stage(A1, R2, Ch, Ch, N, (2, 4), (1, 2), 1, stride=2)                # M = 80: 5 tiles of 8 samples
+    s3 = local_stage(R2, R3, Ch, Ch, N, (1, 2), (2, 4), 1, up=1)                    # 20 tiles of 2 samples = 4 source rows
+    rc, st, deps, nflags, ws, cnt, grid, lds = plan([s0, s1, s2, s3])
+    assert rc == 0 and ws == 0 and cnt == 0
+    assert [s.n_items for s in st] == [20 * NS, 10 * NS, 5 * NS, 20 * NS]
+    assert [s.n_flags for s in st] == [20 * NS, 20 * NS, 5 * NS, 20 * NS] and nflags == 65 * NS
+    assert all(local_item_deps(st[0], deps, i) == [[], [], [], []] for i in range(st[0].n_items))
+    src_tiles = {1: lambda rg: (2 * rg, 2 * rg + 1),          # 32 rows = 4 samples: the producer's tiles 2 rg, 2 rg + 1
+                 2: lambda rg: tuple(range(4 * rg, 4 * rg + 4)),      # 8 samples of 8 source rows = 64 rows
+                 3: lambda rg: (rg // 4,)}                    # 2 samples of 2 source rows = 4 rows of a 16-row tile
+    for k in (1, 2, 3):
+        prod = st[k - 1]
+        MTp = prod.n_flags // NS                                 # the producer's 16-row tiles
+        for item in range(st[k].n_items):
+            rg, sl = divmod(item, NS)
+            want = [sorted(prod.flag_base + c * MTp + t for c in (2 * w, 2 * w + 1) for t in src_tiles[k](rg)) for w in range(4)]
+            assert local_item_deps(st[k], deps, item) == want, (k, item)
 
 
 def test_cfgB_plan_becomes_two_sample_local_chains_with_a_skip_side():

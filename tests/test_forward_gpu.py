@@ -1,7 +1,7 @@
 """Full ``UNetVideoModel.forward`` on the MI355X vs the golden vectors of the REAL reference and
 vs the CPU oracle (same seeded inputs, closed-form parameters).  GPU only.
 
-Stated fp32 tolerance for one forward: |d| <= 2e-4 + 1e-3*|ref| (the reference's
+Stated fp32 tolerance for one forward: |d| <= 1e-4 + 1e-3*|ref| (the reference's
 own fp32 CPU result sits 4e-5..1.4e-4 from an fp64 evaluation of the same network).
 """
 import os
@@ -12,7 +12,7 @@ import torch
 
 from oracle import recipe, unet_oracle as uo
 from conftest import GOLDEN
-from test_oracle_golden import CONFIGS, load_case
+from test_oracle_golden import CONFIGS, NONSQUARE, compare_to_fixture, load_case, load_nonsquare
 
 pytestmark = pytest.mark.gpu
 
@@ -48,10 +48,28 @@ def test_forward_vs_reference_golden(name):
     ref = torch.from_numpy(g["out"])
     err = float((out.cpu() - ref).abs().max())
     print(f"[{name}] max|hip - reference| = {err:.3e} (max|ref| {float(ref.abs().max()):.3f})")
-    assert torch.allclose(out.cpu(), ref, atol=2e-4, rtol=1e-3), err
+    assert torch.allclose(out.cpu(), ref, atol=1e-4, rtol=1e-3), err          # the contract of SURVEY §8c
     np.testing.assert_allclose(attn["temporal"][0].cpu().numpy()[:8], g["attn_t0"], atol=1e-4)
     np.testing.assert_allclose(attn["spatial"][0].cpu().numpy()[:1, :32, :32], g["attn_s0"], atol=1e-4)
     assert len(attn["temporal"]) == len(attn["spatial"]) and attn["mixed"] == []
+
+
+@pytest.mark.parametrize("name", list(NONSQUARE))
+def test_nonsquare_forward_vs_fp64_fixture(name):
+    """``model(x)`` at latents whose levels are not square (16x32, 32x16: down to 2x4 / 4x2; 8x24: 8x24 ... 1x3, no level a
+    power of two) and at the reference's defaults for 4x32x32 latents (ch128, two ResBlocks per level, attention at 16x16
+    and 8x8) against fp64 fixtures (oracle/make_golden.py::gen_forward_nonsquare), at the contract tolerance."""
+    g = np.load(os.path.join(GOLDEN, f"forward_{name}.npz"))
+    cfg, sd, inp = load_nonsquare(name)
+    assert int(g["n_params"]) == sum(v.numel() for v in sd.values())
+    model = build_native(cfg, sd)
+    d = {k: v.cuda() for k, v in inp.items()}
+    with torch.no_grad():
+        out, _ = model(d["x"], x0=d["x0"], timesteps=d["t"].float(), frame_indices=d["frame_indices"],
+                       obs_mask=d["obs_mask"], latent_mask=d["latent_mask"])
+    assert out.shape == inp["x"].shape[:2] + (cfg["out_channels"],) + inp["x"].shape[3:]
+    err = compare_to_fixture(out, g, atol=1e-4, rtol=1e-3)
+    print(f"[{name}] model(x) max|hip - fp64| = {err:.3e} (max|ref| {float(g['absmax']):.3f})")
 
 
 def test_forward_error_vs_fp64_truth():

@@ -55,6 +55,16 @@ def packed(nat, w):
     return o
 
 
+def hw(H):
+    """A map size parameter: an int (square map) or (rows, columns)."""
+    return (H, H) if isinstance(H, int) else tuple(H)
+
+
+def nsq(*vals):
+    """A parametrization row whose map is (rows, columns): id "a-b-RxC-..." (the square rows keep their ids)."""
+    return pytest.param(*vals, id="-".join(f"{v[0]}x{v[1]}" if isinstance(v, tuple) else str(v) for v in vals))
+
+
 @pytest.mark.parametrize("N,Cin,Cout,H", [(3, 64, 64, 16), (5, 128, 96, 8), (40, 256, 128, 2), (2, 32, 4, 16),
                                           (1, 64, 192, 5)])
 def test_conv3x3_plain(nat, N, Cin, Cout, H):
@@ -919,20 +929,26 @@ def test_sampler_tick(nat):
 
 @pytest.mark.parametrize("N,Cin,Cout,H,k,stride", [(3, 64, 64, 16, 3, 1), (2, 128, 192, 5, 3, 1), (5, 64, 64, 8, 3, 2),
                                                    (7, 128, 32, 6, 1, 1), (40, 128, 128, 4, 3, 1), (4, 64, 4, 16, 3, 1),
-                                                   (21, 256, 128, 16, 3, 1)])
+                                                   (21, 256, 128, 16, 3, 1),
+                                                   nsq(5, 64, 64, (2, 4), 3, 1), nsq(40, 128, 128, (4, 2), 3, 1),
+                                                   nsq(3, 128, 96, (4, 8), 3, 1), nsq(3, 64, 64, (8, 16), 3, 1),
+                                                   nsq(3, 64, 64, (16, 8), 3, 1), nsq(7, 64, 96, (6, 10), 3, 1),
+                                                   nsq(13, 128, 64, (1, 3), 3, 1), nsq(5, 64, 64, (8, 16), 3, 2),
+                                                   nsq(3, 128, 64, (6, 10), 3, 2), nsq(9, 128, 32, (10, 6), 1, 1)])
 def test_conv_every_tune_code(nat, N, Cin, Cout, H, k, stride):
     """Every legal launch variant - register-staged and LDS-DMA (buffer_load ... lds, 2 and 3 stages), both K-chunk
     widths, split-K and tail-split - computes the same convolution (odd sizes: ragged last tiles, image borders)."""
     import ctypes as C
     pad = 1 if k == 3 else 0
-    x, w, b = rnd("et/x", N, Cin, H, H), rnd("et/w", Cout, Cin, k, k, scale=0.05), rnd("et/b", Cout)
+    H, W = hw(H)
+    x, w, b = rnd("et/x", N, Cin, H, W), rnd("et/w", Cout, Cin, k, k, scale=0.05), rnd("et/b", Cout)
     ref = F.conv2d(x, w, b, padding=pad, stride=stride)
-    Ho = ref.shape[2]
-    out = torch.empty(N * Ho * Ho, Cout, device="cuda")
+    Ho, Wo = ref.shape[2:]
+    out = torch.empty(N * Ho * Wo, Cout, device="cuda")
     ws = torch.empty(1 << 22, device="cuda")
     cnt = torch.zeros(4096, dtype=torch.int32, device="cuda")
     keep = dict(src0=cl(x), W=packed(nat, w), bias=b.cuda())
-    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=H, Ho=Ho, Wo=Ho, Cout=Cout, out=out, ldo=Cout, ksize=k, stride=stride, **keep)
+    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=W, Ho=Ho, Wo=Wo, Cout=Cout, out=out, ldo=Cout, ksize=k, stride=stride, **keep)
     a.splitk_ws, a.splitk_cnt, a.splitk_ws_floats, a.splitk_cnt_ints = ws.data_ptr(), cnt.data_ptr(), ws.numel(), cnt.numel()
     codes = (C.c_int * 256)()
     n = nat.lib().lfvdm_conv_igemm_candidates(C.byref(a), codes, 256)
@@ -942,32 +958,36 @@ def test_conv_every_tune_code(nat, N, Cin, Cout, H, k, stride):
         a.tune = code
         out.fill_(float("nan"))
         nat.conv_igemm_struct(a)
-        got = from_cl(out, N, Ho, Ho, Cout)
+        got = from_cl(out, N, Ho, Wo, Cout)
         err = float((got.cpu() - ref).abs().max())
         assert err < 5e-5, f"tune code {code}: max|d| = {err:.3e}"
     assert int(cnt.abs().sum()) == 0, "split-K tickets must be left at zero"
 
 
 @pytest.mark.parametrize("N,Cin,Cout,H,up", [(3, 64, 64, 8, 1), (2, 128, 96, 5, 1), (40, 128, 128, 2, 1), (3, 64, 64, 7, 2),
-                                             (5, 128, 64, 4, 2)])
+                                             (5, 128, 64, 4, 2),
+                                             nsq(40, 128, 128, (1, 2), 1), nsq(3, 64, 64, (2, 4), 1), nsq(2, 128, 96, (4, 8), 1),
+                                             nsq(3, 64, 64, (8, 4), 1), nsq(7, 64, 64, (3, 5), 1), nsq(13, 64, 64, (1, 3), 1),
+                                             nsq(3, 64, 64, (4, 8), 2), nsq(5, 128, 64, (8, 4), 2), nsq(7, 64, 64, (3, 5), 2)])
 def test_conv_upsampled_source_every_tune_code(nat, N, Cin, Cout, H, up):
     """3x3 conv over a nearest-2x upsampled source (Upsample, unet.py:60-83) and over a zero-inserted one (the data
     gradient of a stride-2 conv as a transposed convolution): every launch variant, including the LDS-DMA loop whose
     per-lane source offsets are rebuilt per tap for these two modes."""
     import ctypes as C
-    x, w, b = rnd("eu/x", N, Cin, H, H), rnd("eu/w", Cout, Cin, 3, 3, scale=0.05), rnd("eu/b", Cout)
+    H, W = hw(H)
+    x, w, b = rnd("eu/x", N, Cin, H, W), rnd("eu/w", Cout, Cin, 3, 3, scale=0.05), rnd("eu/b", Cout)
     if up == 1:
         xin = F.interpolate(x, scale_factor=2, mode="nearest")
     else:
-        xin = torch.zeros(N, Cin, 2 * H, 2 * H)
+        xin = torch.zeros(N, Cin, 2 * H, 2 * W)
         xin[:, :, ::2, ::2] = x
     ref = F.conv2d(xin, w, b, padding=1)
-    Ho = 2 * H
-    out = torch.empty(N * Ho * Ho, Cout, device="cuda")
+    Ho, Wo = 2 * H, 2 * W
+    out = torch.empty(N * Ho * Wo, Cout, device="cuda")
     ws = torch.empty(1 << 22, device="cuda")
     cnt = torch.zeros(4096, dtype=torch.int32, device="cuda")
     keep = dict(src0=cl(x), W=packed(nat, w), bias=b.cuda())
-    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=H, Ho=Ho, Wo=Ho, Cout=Cout, out=out, ldo=Cout, ksize=3, up=up, **keep)
+    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=W, Ho=Ho, Wo=Wo, Cout=Cout, out=out, ldo=Cout, ksize=3, up=up, **keep)
     a.splitk_ws, a.splitk_cnt, a.splitk_ws_floats, a.splitk_cnt_ints = ws.data_ptr(), cnt.data_ptr(), ws.numel(), cnt.numel()
     codes = (C.c_int * 256)()
     n = nat.lib().lfvdm_conv_igemm_candidates(C.byref(a), codes, 256)
@@ -977,29 +997,33 @@ def test_conv_upsampled_source_every_tune_code(nat, N, Cin, Cout, H, up):
         a.tune = code
         out.fill_(float("nan"))
         nat.conv_igemm_struct(a)
-        err = float((from_cl(out, N, Ho, Ho, Cout).cpu() - ref).abs().max())
+        err = float((from_cl(out, N, Ho, Wo, Cout).cpu() - ref).abs().max())
         assert err < 5e-5, f"tune code {code}: max|d| = {err:.3e}"
     assert int(cnt.abs().sum()) == 0
 
 
-@pytest.mark.parametrize("N,Cin,Cout,H", [(3, 64, 64, 7), (40, 128, 128, 2), (2, 96, 160, 16)])
+@pytest.mark.parametrize("N,Cin,Cout,H", [(3, 64, 64, 7), (40, 128, 128, 2), (2, 96, 160, 16),
+                                          nsq(3, 64, 64, (2, 4)), nsq(40, 128, 128, (1, 2)), nsq(5, 64, 64, (4, 8)),
+                                          nsq(2, 96, 160, (8, 16)), nsq(3, 64, 64, (8, 4)), nsq(7, 64, 64, (3, 5)),
+                                          nsq(13, 64, 64, (1, 3))])
 def test_conv_zero_inserted_source_with_residual(nat, N, Cin, Cout, H):
     """The zero-inserted source is computed by output parity classes (rows enumerated on the source grid, 1 / 2 / 2 / 4
     live taps): the residual and the output rows go through the class -> output-row map, so check a launch with a
     residual - what the data gradient of a Downsample conv with a skip connection's gradient riding along issues -
     over every launch variant, against a dense convolution of the explicitly zero-filled image."""
     import ctypes as C
-    x, w = rnd("ez/x", N, Cin, H, H), rnd("ez/w", Cout, Cin, 3, 3, scale=0.05)
-    Ho = 2 * H
-    r = rnd("ez/r", N, Cout, Ho, Ho)
-    xin = torch.zeros(N, Cin, Ho, Ho)
+    H, W = hw(H)
+    x, w = rnd("ez/x", N, Cin, H, W), rnd("ez/w", Cout, Cin, 3, 3, scale=0.05)
+    Ho, Wo = 2 * H, 2 * W
+    r = rnd("ez/r", N, Cout, Ho, Wo)
+    xin = torch.zeros(N, Cin, Ho, Wo)
     xin[:, :, ::2, ::2] = x
     ref = F.conv2d(xin, w, None, padding=1) + r
-    out = torch.empty(N * Ho * Ho, Cout, device="cuda")
+    out = torch.empty(N * Ho * Wo, Cout, device="cuda")
     ws = torch.empty(1 << 22, device="cuda")
     cnt = torch.zeros(4096, dtype=torch.int32, device="cuda")
     keep = dict(src0=cl(x), W=packed(nat, w), res=cl(r))
-    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=H, Ho=Ho, Wo=Ho, Cout=Cout, out=out, ldo=Cout, ksize=3, up=2, ldr=Cout, **keep)
+    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=W, Ho=Ho, Wo=Wo, Cout=Cout, out=out, ldo=Cout, ksize=3, up=2, ldr=Cout, **keep)
     a.splitk_ws, a.splitk_cnt, a.splitk_ws_floats, a.splitk_cnt_ints = ws.data_ptr(), cnt.data_ptr(), ws.numel(), cnt.numel()
     codes = (C.c_int * 256)()
     n = nat.lib().lfvdm_conv_igemm_candidates(C.byref(a), codes, 256)
@@ -1008,41 +1032,46 @@ def test_conv_zero_inserted_source_with_residual(nat, N, Cin, Cout, H):
         a.tune = code
         out.fill_(float("nan"))
         nat.conv_igemm_struct(a)
-        err = float((from_cl(out, N, Ho, Ho, Cout).cpu() - ref).abs().max())
+        err = float((from_cl(out, N, Ho, Wo, Cout).cpu() - ref).abs().max())
         assert err < 5e-5, f"tune code {code}: max|d| = {err:.3e}"
     assert int(cnt.abs().sum()) == 0
 
 
 @pytest.mark.parametrize("N,C0,C1,S0,S1,Cout,H", [(5, 64, 32, 64, 32, 64, 8), (3, 128, 0, 96, 32, 96, 5), (40, 64, 64, 0, 0, 128, 4),
-                                                  (2, 32, 32, 32, 0, 32, 16)])
+                                                  (2, 32, 32, 32, 0, 32, 16),
+                                                  nsq(5, 64, 32, 64, 32, 64, (2, 4)), nsq(40, 64, 64, 0, 0, 128, (4, 2)),
+                                                  nsq(40, 128, 0, 128, 128, 128, (2, 4)), nsq(3, 64, 64, 64, 0, 64, (4, 8)),
+                                                  nsq(2, 32, 32, 32, 0, 32, (8, 16)), nsq(3, 64, 0, 64, 64, 64, (16, 8)),
+                                                  nsq(3, 128, 0, 96, 32, 96, (6, 10)), nsq(13, 64, 0, 0, 0, 64, (1, 3))])
 def test_conv_concat_and_skip_segment_every_tune_code(nat, N, C0, C1, S0, S1, Cout, H):
     """Virtual concat (src0 | src1) 3x3 conv + fused 1x1 skip segment on a second raw concat (s2src0 | s2src1) +
     residual (the second conv of a channel-changing ResBlock, unet.py:173-207): every launch variant, including the
     general LDS-DMA loop with its per-chunk descriptor selects, gives the same result."""
     import ctypes as C
     Cin, C2 = C0 + C1, S0 + S1
-    x, w, b = rnd("cs2/x", N, Cin, H, H), rnd("cs2/w", Cout, Cin, 3, 3, scale=0.05), rnd("cs2/b", Cout)
+    H, W = hw(H)
+    x, w, b = rnd("cs2/x", N, Cin, H, W), rnd("cs2/w", Cout, Cin, 3, 3, scale=0.05), rnd("cs2/b", Cout)
     ref = F.conv2d(x, w, b, padding=1)
     keep = dict(src0=cl(x[:, :C0]), W=packed(nat, w), bias=b.cuda())
     kw = dict(C0=C0, C1=C1)
     if C1:
         keep["src1"] = cl(x[:, C0:])
     if C2:
-        s, w2, b2 = rnd("cs2/s", N, C2, H, H), rnd("cs2/w2", Cout, C2, scale=0.05), rnd("cs2/b2", Cout)
+        s, w2, b2 = rnd("cs2/s", N, C2, H, W), rnd("cs2/w2", Cout, C2, scale=0.05), rnd("cs2/b2", Cout)
         ref = ref + F.conv2d(s, w2.view(Cout, C2, 1, 1), b2)
         keep.update(s2src0=cl(s[:, :S0]), W2=w2.cuda().contiguous(), bias2=b2.cuda())
         kw.update(s2C0=S0, s2C1=S1)
         if S1:
             keep["s2src1"] = cl(s[:, S0:])
     else:
-        r = rnd("cs2/r", N * H * H, Cout)
-        ref = ref + r.view(N, H, H, Cout).permute(0, 3, 1, 2)
+        r = rnd("cs2/r", N * H * W, Cout)
+        ref = ref + r.view(N, H, W, Cout).permute(0, 3, 1, 2)
         keep["res"] = r.cuda()
         kw["ldr"] = Cout
-    out = torch.empty(N * H * H, Cout, device="cuda")
+    out = torch.empty(N * H * W, Cout, device="cuda")
     ws = torch.empty(1 << 22, device="cuda")
     cnt = torch.zeros(4096, dtype=torch.int32, device="cuda")
-    a = nat.fill_conv_args(N=N, Hs=H, Ws=H, Ho=H, Wo=H, Cout=Cout, out=out, ldo=Cout, **kw, **keep)
+    a = nat.fill_conv_args(N=N, Hs=H, Ws=W, Ho=H, Wo=W, Cout=Cout, out=out, ldo=Cout, **kw, **keep)
     a.splitk_ws, a.splitk_cnt, a.splitk_ws_floats, a.splitk_cnt_ints = ws.data_ptr(), cnt.data_ptr(), ws.numel(), cnt.numel()
     codes = (C.c_int * 256)()
     n = nat.lib().lfvdm_conv_igemm_candidates(C.byref(a), codes, 256)
@@ -1051,14 +1080,20 @@ def test_conv_concat_and_skip_segment_every_tune_code(nat, N, C0, C1, S0, S1, Co
         a.tune = code
         out.fill_(float("nan"))
         nat.conv_igemm_struct(a)
-        err = float((from_cl(out, N, H, H, Cout).cpu() - ref).abs().max())
+        err = float((from_cl(out, N, H, W, Cout).cpu() - ref).abs().max())
         assert err < 5e-5, f"tune code {code}: max|d| = {err:.3e}"
 
 
 @pytest.mark.parametrize("N,C0,C1,Cout,H,k,stride,up", [(10, 128, 0, 128, 16, 3, 1, 0), (5, 64, 0, 96, 5, 3, 1, 0),
                                                         (6, 64, 64, 160, 8, 1, 1, 0), (4, 64, 0, 64, 8, 3, 2, 0),
                                                         (3, 128, 0, 128, 4, 3, 1, 1), (40, 256, 0, 128, 2, 3, 1, 0),
-                                                        (2, 32, 0, 32, 6, 3, 1, 0)])
+                                                        (2, 32, 0, 32, 6, 3, 1, 0),
+                                                        nsq(5, 128, 0, 128, (4, 8), 3, 1, 0), nsq(3, 64, 64, 128, (12, 8), 3, 1, 0),
+                                                        nsq(6, 128, 0, 96, (2, 16), 3, 1, 0), nsq(3, 128, 0, 128, (6, 16), 3, 1, 0),
+                                                        nsq(2, 64, 0, 64, (16, 32), 3, 1, 0), nsq(3, 64, 0, 64, (8, 24), 3, 1, 0),
+                                                        nsq(7, 64, 0, 64, (6, 10), 3, 1, 0), nsq(4, 64, 0, 64, (8, 16), 3, 2, 0),
+                                                        nsq(3, 64, 0, 96, (6, 10), 3, 2, 0), nsq(3, 128, 0, 128, (2, 4), 3, 1, 1),
+                                                        nsq(13, 64, 0, 32, (1, 3), 3, 1, 0), nsq(5, 64, 64, 160, (4, 8), 1, 1, 0)])
 @pytest.mark.parametrize("variant", ["dma3", "dma2", "regs"])
 def test_conv_wgrad_matches_autograd(nat, monkeypatch, N, C0, C1, Cout, H, k, stride, up, variant):
     """lfvdm_conv_wgrad (weight + bias gradient of Conv2d / Linear, train_util.py:328 loss.backward()) vs torch
@@ -1072,17 +1107,18 @@ def test_conv_wgrad_matches_autograd(nat, monkeypatch, N, C0, C1, Cout, H, k, st
     else:
         monkeypatch.setenv("LFVDM_WGRAD_STAGES", variant[-1])
     Cin = C0 + C1
-    x = rnd("wg/x", N, Cin, H, H)
+    H, W = hw(H)
+    x = rnd("wg/x", N, Cin, H, W)
     w = (rnd("wg/w", Cout, Cin, k, k, scale=0.05)).requires_grad_(True)
     b = rnd("wg/b", Cout).requires_grad_(True)
     xin = F.interpolate(x, scale_factor=2, mode="nearest") if up else x
     y = F.conv2d(xin, w, b, padding=1 if k == 3 else 0, stride=stride)
-    Ho = y.shape[2]
-    dout = rnd("wg/d", N, Cout, Ho, Ho)
+    Ho, Wo = y.shape[2:]
+    dout = rnd("wg/d", N, Cout, Ho, Wo)
     y.backward(dout)
     gp = torch.zeros(Cout, k * k, Cin, device="cuda")
     db = torch.zeros(Cout, device="cuda")
-    kw = dict(src0=cl(x[:, :C0]), C0=C0, C1=C1, N=N, Hs=H, Ws=H, Ho=Ho, Wo=Ho, ksize=k, stride=stride, up=up,
+    kw = dict(src0=cl(x[:, :C0]), C0=C0, C1=C1, N=N, Hs=H, Ws=W, Ho=Ho, Wo=Wo, ksize=k, stride=stride, up=up,
               res=cl(dout), ldr=Cout, out=gp, bias=db, Cout=Cout)
     if C1:
         kw["src1"] = cl(x[:, C0:])
@@ -1095,14 +1131,20 @@ def test_conv_wgrad_matches_autograd(nat, monkeypatch, N, C0, C1, Cout, H, k, st
 
 @pytest.mark.parametrize("N,Cin,Cout,H,film,skip_raw,k", [(6, 64, 128, 8, True, True, 3), (8, 128, 128, 4, True, False, 3),
                                                          (40, 128, 64, 2, False, False, 3), (4, 64, 256, 8, True, True, 3),
-                                                         (6, 64, 64, 4, False, False, 1)])
+                                                         (6, 64, 64, 4, False, False, 1),
+                                                         nsq(40, 128, 128, (2, 4), True, False, 3), nsq(40, 128, 64, (4, 2), False, True, 3),
+                                                         nsq(8, 64, 128, (4, 8), True, False, 3), nsq(6, 64, 64, (8, 4), False, False, 1),
+                                                         nsq(10, 64, 256, (1, 2), True, True, 3), nsq(14, 128, 64, (1, 8), True, False, 3),
+                                                         nsq(4, 64, 128, (8, 16), True, False, 3), nsq(4, 64, 64, (16, 8), False, False, 3),
+                                                         nsq(6, 64, 128, (6, 10), True, False, 3), nsq(14, 64, 64, (1, 3), False, False, 3)])
 def test_conv_fused_output_groupnorm_every_tune_code(nat, N, Cin, Cout, H, film, skip_raw, k):
     """Conv + the NEXT layer's GroupNorm32(+FiLM)+SiLU in the conv's epilogue (lfvdm_conv_args gn_*): the second
     normalisation of a ResBlock, unet.py:199-203.  Every offered tile holds whole samples and groups; each variant must
     match conv2d -> group_norm -> scale/shift -> silu in fp64."""
     import ctypes as C
     T = 2
-    x, w, b = rnd("gnf/x", N, Cin, H, H), rnd("gnf/w", Cout, Cin, k, k, scale=0.05), rnd("gnf/b", Cout)
+    H, W = hw(H)
+    x, w, b = rnd("gnf/x", N, Cin, H, W), rnd("gnf/w", Cout, Cin, k, k, scale=0.05), rnd("gnf/b", Cout)
     gamma, beta = 1 + 0.1 * rnd("gnf/g", Cout), 0.1 * rnd("gnf/be", Cout)
     fm = 0.3 * rnd("gnf/film", N // T, 2 * Cout) if film else None
     raw = F.conv2d(x.double(), w.double(), b.double(), padding=1 if k == 3 else 0)
@@ -1111,17 +1153,26 @@ def test_conv_fused_output_groupnorm_every_tune_code(nat, N, Cin, Cout, H, film,
         f = fm.double().repeat_interleave(T, dim=0)
         ref = ref * (1 + f[:, :Cout, None, None]) + f[:, Cout:, None, None]
     ref = F.silu(ref).float()
-    out = torch.empty(N * H * H, Cout, device="cuda")
-    gn_out = torch.empty(N * H * H, Cout, device="cuda")
+    out = torch.empty(N * H * W, Cout, device="cuda")
+    gn_out = torch.empty(N * H * W, Cout, device="cuda")
     ws = torch.empty(1 << 22, device="cuda")
     cnt = torch.zeros(4096, dtype=torch.int32, device="cuda")
     keep = dict(src0=cl(x), W=packed(nat, w), bias=b.cuda(), gn_gamma=gamma.cuda(), gn_beta=beta.cuda(),
                 gn_film=fm.cuda() if film else None)
-    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=H, Ho=H, Wo=H, Cout=Cout, out=out, ldo=Cout, ksize=k, gn_out=gn_out,
+    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=W, Ho=H, Wo=W, Cout=Cout, out=out, ldo=Cout, ksize=k, gn_out=gn_out,
                            gn_film_div=T, gn_act=nat.ACT_SILU, gn_skip_raw=skip_raw, **keep)
     a.splitk_ws, a.splitk_cnt, a.splitk_ws_floats, a.splitk_cnt_ints = ws.data_ptr(), cnt.data_ptr(), ws.numel(), cnt.numel()
     codes = (C.c_int * 256)()
     n = nat.lib().lfvdm_conv_igemm_candidates(C.byref(a), codes, 256)
+    # a tile must hold whole samples (P = H*W divides its 32 or 64 rows); a map that fits none must be refused, not silently
+    # wrong (8x16, 16x8: 128 rows per sample; 6x10, 1x3: P does not divide a tile)
+    if 64 % (H * W):
+        assert n == 0
+        for general in (0, 1):
+            a.tune, a.gn_general = 0, general
+            with pytest.raises(RuntimeError):
+                nat.conv_igemm_struct(a)
+        return
     assert n > 0
     # both forms of the epilogue: registers + lane butterflies (P and Cout/32 powers of two: every case here) and the general
     # LDS-tile form (gn_general, what other shapes get)
@@ -1129,12 +1180,12 @@ def test_conv_fused_output_groupnorm_every_tune_code(nat, N, Cin, Cout, H, film,
         a.tune, a.gn_general = code, general
         out.fill_(float("nan")); gn_out.fill_(float("nan"))
         nat.conv_igemm_struct(a)
-        err = float((from_cl(gn_out, N, H, H, Cout).cpu() - ref).abs().max())
+        err = float((from_cl(gn_out, N, H, W, Cout).cpu() - ref).abs().max())
         assert err < 1e-4, f"tune code {code}, general form {general}: fused GroupNorm max|d| = {err:.3e}"
         if skip_raw:
             assert bool(torch.isnan(out).all()), "raw output must not be written with gn_skip_raw"
         else:
-            assert float((from_cl(out, N, H, H, Cout).cpu() - raw.float()).abs().max()) < 5e-5
+            assert float((from_cl(out, N, H, W, Cout).cpu() - raw.float()).abs().max()) < 5e-5
     # a 16x16 map (256 rows per sample) fits no tile: the launch must be refused, not silently wrong
     x2 = rnd("gnf/x2", 2, Cin, 16, 16)
     o2 = torch.empty(2 * 256, Cout, device="cuda")
@@ -1350,7 +1401,12 @@ def test_gn_backward_large_maps(nat, N, P, C0, C1, film, act, adds, mode, monkey
 
 
 @pytest.mark.parametrize("N,C0,C1,Cout,H,k", [(10, 128, 0, 128, 16, 3), (3, 128, 128, 256, 8, 3), (4, 256, 0, 128, 8, 1),
-                                              (2, 128, 0, 160, 12, 3), (1, 64, 64, 96, 32, 3), (2, 128, 0, 128, 64, 3)])
+                                              (2, 128, 0, 160, 12, 3), (1, 64, 64, 96, 32, 3), (2, 128, 0, 128, 64, 3),
+                                              nsq(5, 128, 0, 128, (4, 8), 3), nsq(3, 128, 128, 256, (12, 8), 3),
+                                              nsq(6, 128, 0, 160, (2, 16), 3), nsq(3, 64, 64, 128, (6, 16), 3),
+                                              nsq(2, 128, 0, 128, (16, 32), 3), nsq(3, 128, 0, 128, (8, 24), 3),
+                                              nsq(7, 128, 0, 128, (6, 10), 3), nsq(4, 256, 0, 128, (8, 16), 1),
+                                              nsq(13, 128, 0, 64, (1, 3), 3)])
 def test_conv_wgrad_every_tune_code(nat, N, C0, C1, Cout, H, k):
     """Every launch code the weight-gradient tuner may pick for a layer shape (_native._wgrad_codes: 64- / 128-filter tiles,
     the 128 x 128 tile of code 3, two / three LDS-DMA stages, 64-row chunks, M slices, and - 3x3 layers on maps of 8, 16 or a
@@ -1358,23 +1414,24 @@ def test_conv_wgrad_every_tune_code(nat, N, C0, C1, Cout, H, k):
     torch autograd; the tap-fused kernels also through the deterministic slabs, bitwise reproducibly."""
     import ctypes as C
     Cin = C0 + C1
-    x = rnd("wgc/x", N, Cin, H, H)
+    H, W = hw(H)
+    x = rnd("wgc/x", N, Cin, H, W)
     w = (rnd("wgc/w", Cout, Cin, k, k, scale=0.05)).requires_grad_(True)
     b = rnd("wgc/b", Cout).requires_grad_(True)
     y = F.conv2d(x, w, b, padding=1 if k == 3 else 0)
-    dout = rnd("wgc/d", N, Cout, H, H)
+    dout = rnd("wgc/d", N, Cout, H, W)
     y.backward(dout)
     gp = torch.zeros(Cout, k * k, Cin, device="cuda")
     db = torch.zeros(Cout, device="cuda")
     keep = dict(src0=cl(x[:, :C0]), res=cl(dout))
     if C1:
         keep["src1"] = cl(x[:, C0:])
-    a = nat.fill_conv_args(C0=C0, C1=C1, N=N, Hs=H, Ws=H, Ho=H, Wo=H, ksize=k, ldr=Cout, out=gp, bias=db, Cout=Cout, **keep)
+    a = nat.fill_conv_args(C0=C0, C1=C1, N=N, Hs=H, Ws=W, Ho=H, Wo=W, ksize=k, ldr=Cout, out=gp, bias=db, Cout=Cout, **keep)
     codes = nat._wgrad_codes(a)
     tiles = {(c - 1) & 3 for c in codes if ((c - 1) >> 2) & 3}
     assert ({1, 2, 3} if Cin % 128 == 0 and C0 % 128 == 0 and Cout >= 128 else {1}) <= tiles, tiles
     taps_codes = [c for c in codes if ((c - 1) >> 2) & 3 == 0]
-    eligible = k == 3 and (H * H) % 32 == 0 and (H % 32 == 0 or H in (8, 16))
+    eligible = k == 3 and (H * W) % 32 == 0 and (W % 32 == 0 or W in (8, 16))      # the row-segment instance is chosen by Wo
     assert bool(taps_codes) == eligible and (not eligible or {(c - 1) & 3 for c in taps_codes} == {1, 2})
     scale = max(1.0, float(w.grad.abs().max()))
     for code in [0] + codes:
@@ -1487,7 +1544,11 @@ def test_conv_wgrad_oihw_output_every_tune_code(nat):
         assert float((db.cpu() - b.grad).abs().max()) < 2e-5 * max(1.0, float(b.grad.abs().max())), f"tune code {code}: db"
 
 
-@pytest.mark.parametrize("N,Cin,C0,C1,H", [(40, 128, 128, 128, 2), (8, 256, 128, 128, 4), (6, 64, 64, 64, 4), (4, 128, 256, 256, 2)])
+@pytest.mark.parametrize("N,Cin,C0,C1,H", [(40, 128, 128, 128, 2), (8, 256, 128, 128, 4), (6, 64, 64, 64, 4), (4, 128, 256, 256, 2),
+                                           nsq(40, 128, 128, 128, (2, 4)), nsq(40, 128, 128, 128, (4, 2)),
+                                           nsq(8, 128, 64, 64, (4, 8)), nsq(13, 128, 128, 128, (1, 2)),
+                                           nsq(6, 64, 64, 64, (8, 16)), nsq(4, 64, 64, 64, (16, 8)),
+                                           nsq(5, 128, 128, 128, (6, 10)), nsq(14, 64, 64, 64, (1, 3))])
 def test_concat_groupnorm_half_by_half_every_tune_code(nat, N, Cin, C0, C1, H):
     """The decoder's first normalisation, GroupNorm32 + SiLU over concat(h, skip) (unet.py:460 + :152-155), evaluated half by
     half: h = conv3x3(x) normalised in the producing GEMM's epilogue with the CONCAT's group width (lfvdm_conv_args.gn_gw,
@@ -1495,14 +1556,15 @@ def test_concat_groupnorm_half_by_half_every_tune_code(nat, N, Cin, C0, C1, H):
     straddles the concat when (C0 + C1) / 32 divides both halves, so the result must equal F.group_norm of the materialised
     concat in fp64 - for every tile code the tuner may pick, in both forms of the epilogue."""
     import ctypes as C
-    x, w, b = rnd("cat/x", N, Cin, H, H), rnd("cat/w", C0, Cin, 3, 3, scale=0.05), rnd("cat/b", C0)
-    skip = rnd("cat/skip", N, C1, H, H)
+    H, W = hw(H)
+    x, w, b = rnd("cat/x", N, Cin, H, W), rnd("cat/w", C0, Cin, 3, 3, scale=0.05), rnd("cat/b", C0)
+    skip = rnd("cat/skip", N, C1, H, W)
     Cc = C0 + C1
     gw = Cc // 32
     gamma, beta = 1 + 0.1 * rnd("cat/g", Cc), 0.1 * rnd("cat/be", Cc)
     h = F.conv2d(x.double(), w.double(), b.double(), padding=1)
     ref = F.silu(F.group_norm(torch.cat([h, skip.double()], 1), 32, gamma.double(), beta.double(), eps=1e-5)).float()
-    M, P = N * H * H, H * H
+    M, P = N * H * W, H * W
     act = torch.full((M, Cc), float("nan"), device="cuda")
     raw = torch.empty(M, C0, device="cuda")
     g_dev, b_dev = gamma.cuda(), beta.cuda()
@@ -1512,19 +1574,27 @@ def test_concat_groupnorm_half_by_half_every_tune_code(nat, N, Cin, C0, C1, H):
     ws = torch.empty(1 << 22, device="cuda")
     cnt = torch.zeros(4096, dtype=torch.int32, device="cuda")
     keep = dict(src0=cl(x), W=packed(nat, w), bias=b.cuda())
-    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=H, Ho=H, Wo=H, Cout=C0, out=raw, ldo=C0, gn_out=act, gn_gamma=g_dev, gn_beta=b_dev,
+    a = nat.fill_conv_args(C0=Cin, N=N, Hs=H, Ws=W, Ho=H, Wo=W, Cout=C0, out=raw, ldo=C0, gn_out=act, gn_gamma=g_dev, gn_beta=b_dev,
                            gn_film_div=1, gn_act=nat.ACT_SILU, gn_skip_raw=0, **keep)
     a.gn_gw, a.gn_ld = gw, Cc
     a.splitk_ws, a.splitk_cnt, a.splitk_ws_floats, a.splitk_cnt_ints = ws.data_ptr(), cnt.data_ptr(), ws.numel(), cnt.numel()
     codes = (C.c_int * 256)()
     n = nat.lib().lfvdm_conv_igemm_candidates(C.byref(a), codes, 256)
-    assert n > 0
     right = act[:, C0:].clone()
+    if 64 % P:          # no tile holds whole samples of this map: refused, the skip half's columns untouched
+        assert n == 0
+        for general in (0, 1):
+            a.tune, a.gn_general = 0, general
+            with pytest.raises(RuntimeError):
+                nat.conv_igemm_struct(a)
+        assert torch.equal(act[:, C0:], right)
+        return
+    assert n > 0
     for code, general in [(c, g) for c in [0] + [codes[i] for i in range(n)] for g in (0, 1)]:
         a.tune, a.gn_general = code, general
         act[:, :C0].fill_(float("nan"))
         nat.conv_igemm_struct(a)
         assert torch.equal(act[:, C0:], right), "the GEMM's epilogue must not touch the skip half's columns"
-        err = float((from_cl(act, N, H, H, Cc).cpu() - ref).abs().max())
+        err = float((from_cl(act, N, H, W, Cc).cpu() - ref).abs().max())
         assert err < 1e-4, f"tune code {code}, general form {general}: max|d| = {err:.3e}"
-        assert float((from_cl(raw, N, H, H, C0).cpu() - h.float()).abs().max()) < 5e-5
+        assert float((from_cl(raw, N, H, W, C0).cpu() - h.float()).abs().max()) < 5e-5

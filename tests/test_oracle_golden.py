@@ -54,6 +54,65 @@ def test_forward_matches_reference(name):
     np.testing.assert_allclose(attn["spatial"][0].numpy()[:1, :32, :32], g["attn_s0"], atol=5e-5)
 
 
+# Non-square latents (oracle/make_golden.py::NONSQUARE): name -> (cfg kwargs, B, T, H, W, n_pad).  The fixtures hold the
+# fp64 forward, checked against the reference's fp32 forward when they were made.
+NONSQUARE = {
+    "cfgB_16x32": (CONFIGS["cfgB"][0], 2, 20, 16, 32, 3),
+    "cfgB_32x16": (CONFIGS["cfgB"][0], 2, 20, 32, 16, 3),
+    "cfgB_8x24": (CONFIGS["cfgB"][0], 2, 20, 8, 24, 3),
+    "carla32": (dict(model_channels=128, num_res_blocks=2, channel_mult=(1, 2, 2, 2), attention_resolutions=(2, 4), num_heads=4),
+                2, 20, 32, 32, 3),
+}
+
+
+def load_nonsquare(name):
+    kw, B, T, H, W, n_pad = NONSQUARE[name]
+    cfg = uo.make_cfg(**kw)
+    sd = tt(recipe.fill_state_dict(uo.param_shapes(cfg)))
+    inp = tt(recipe.make_inputs(name, B, T, cfg["in_channels"], H, W, n_pad=n_pad))
+    return cfg, sd, inp
+
+
+def compare_to_fixture(out, g, atol, rtol):
+    """max|out - fixture| over what the fixture holds (the whole output, or a subsample + per-(frame, channel) sums and
+    norms of the whole map); asserts |d| <= atol + rtol * |ref| element-wise and on the sums / norms at their scale."""
+    out = out.detach().cpu().double()
+    if "out" in g:
+        ref = torch.from_numpy(g["out"]).double()
+        got = out
+    else:
+        sy, sx = (int(v) for v in g["stride"])
+        ref = torch.from_numpy(g["sub"]).double()
+        got = out[..., ::sy, ::sx]
+        P = out.shape[-1] * out.shape[-2]
+        norm, fsum = out.pow(2).sum(dim=(-1, -2)).sqrt(), out.sum(dim=(-1, -2))
+        gn, gs = torch.from_numpy(g["frame_norm"]), torch.from_numpy(g["frame_sum"])
+        assert bool(((norm - gn).abs() <= atol * P ** 0.5 + rtol * gn.abs()).all()), float((norm - gn).abs().max())
+        assert bool(((fsum - gs).abs() <= atol * P + rtol * gn.abs() * P ** 0.5).all()), float((fsum - gs).abs().max())
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    err = float((got - ref).abs().max())
+    assert bool(((got - ref).abs() <= atol + rtol * ref.abs()).all()), err
+    return err
+
+
+@pytest.mark.parametrize("name", ["cfgB_16x32", "cfgB_32x16", "cfgB_8x24"])
+def test_nonsquare_forward_matches_the_fp64_fixture(name):
+    """The oracle in float64 at non-square latents (every level of 16x32 / 32x16 / 8x24 keeps H != W down to 2x4 / 4x2 /
+    1x3) against the fixture: the same fp64 evaluation, so the pin is tight."""
+    g = np.load(os.path.join(GOLDEN, f"forward_{name}.npz"))
+    cfg, sd, inp = load_nonsquare(name)
+    assert int(g["n_params"]) == sum(v.numel() for v in sd.values())
+    assert abs(float(g["x_sum"]) - float(inp["x"].double().sum())) < 1e-6
+    assert np.array_equal(inp["frame_indices"].numpy(), g["frame_indices"])
+    f64 = lambda t: t.double() if t.is_floating_point() else t      # noqa: E731
+    with torch.no_grad():
+        out, _ = uo.unet_forward({k: v.double() for k, v in sd.items()}, cfg, f64(inp["x"]), f64(inp["x0"]), inp["t"].double(),
+                                 inp["frame_indices"], f64(inp["obs_mask"]), f64(inp["latent_mask"]))
+    err = compare_to_fixture(out, g, atol=1e-8, rtol=1e-7)          # (the fixture holds fp32 roundings of fp64 values)
+    print(f"[{name}] fp64 oracle vs fixture max|d| = {err:.2e} (fp32 reference was {float(g['ref_dev']):.2e} away)")
+    assert float(g["ref_dev"]) < 2e-4
+
+
 @pytest.mark.parametrize("name", ["micro", "micro_rb2", "micro_px", "cfgC", "cfgE_T2"])
 def test_backward_matches_reference(name):
     g = np.load(os.path.join(GOLDEN, f"backward_{name}.npz"))

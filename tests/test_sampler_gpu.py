@@ -268,6 +268,40 @@ def test_replayed_cfgB_sampler_plan_follows_the_reference_trajectory():
     assert s.plan.head_fused, "the benchmarked plan ends in the fused output conv + update"
 
 
+@pytest.mark.parametrize("name", ["carla32", "cfgB_16x32"])
+def test_replayed_sampler_at_32x32_and_nonsquare_latents_follows_the_reference_trajectory(name):
+    """The replayed sampler plan (autotuned, level chains, captured step) at the reference's defaults for 4x32x32 latents
+    and at the bench model on a 16x32 latent (sample-local chain stages of two samples per tile) against three steps of
+    the REFERENCE's p_sample from t = 999 with the recorded noise (oracle/make_golden.py::gen_sampler_nonsquare: a
+    subsample plus per-(frame, channel) sums and norms of every step).  Tolerance: 2e-4 per step taken."""
+    from improved_diffusion.gaussian_diffusion import GraphSampler
+    from test_oracle_golden import compare_to_fixture, load_nonsquare
+    g = np.load(os.path.join(GOLDEN, f"sampler_{name}.npz"))
+    cfg, sd, inp = load_nonsquare(name)
+    model = build_native(cfg, sd)
+    diff = make_diffusion(1000, "")
+    d = {k: v.cuda() for k, v in inp.items()}
+    mk = dict(frame_indices=d["frame_indices"], obs_mask=d["obs_mask"], latent_mask=d["latent_mask"], x0=d["x0"])
+    shape = tuple(inp["x"].shape)
+    s = GraphSampler(diff, model, shape, True, inject_noise=True)
+    s.begin(d["x"].clone(), mk)
+    assert s.plan.time_steps == 1000, s.plan.time_table_fallback
+    assert getattr(s.plan, "tuned", False) and s.graph is not None
+    assert s.plan.chains, "the low-resolution levels run as persistent chains"
+    for j, i in enumerate(range(999, 996, -1)):
+        noise = torch.from_numpy(recipe.gaussianish(f"sampler_{name}/noise{j}", inp["x"].numel()).reshape(shape).astype(np.float32))
+        s.noise.copy_(noise.cuda())
+        out = s.step(i)["sample"]
+        torch.cuda.synchronize()
+        gj = {k: g[k][j] for k in ("sub", "frame_sum", "frame_norm")}
+        gj["stride"] = g["stride"]
+        err = compare_to_fixture(out, gj, atol=2e-4 * (j + 1), rtol=0.0)
+        print(f"[{name} replay] step {j} (t={i}): max|d| vs reference trajectory {err:.2e}")
+    assert not s.plan.chains_aborted()
+    if name == "carla32":
+        assert s.plan.head_fused, "the plan ends in the fused output conv + update"
+
+
 def test_fused_head_chain_equals_the_two_launch_chain(monkeypatch):
     """cfg-B sampler with the output conv + update in one launch (lfvdm_conv_out_psample, the default) against the same
     chain with the two launches (LFVDM_FUSED_HEAD=0): same noise stream (same chain seed), so the only difference is the
