@@ -492,6 +492,9 @@ int lfvdm_attn_spatial_fused(const float* xn, const float* Wqkv, const float* bq
 int lfvdm_attn_spatial_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* delta_ws,
                            float* dqkv, int N, int P, int C, int heads, void* stream);
 
+/* Temporal core for T <= 64 frames per window (T > 64: LFVDM_E_SHAPE).  T <= 32 runs the per-window kernels of
+ * attention.hip / attention_temporal2.hip; 33 <= T <= 64 the frame-group kernels of attention_temporal_long.hip
+ * (head dim a multiple of 8, else LFVDM_E_UNSUPPORTED).  The same limits hold for _sel, _ring and _bwd. */
 int lfvdm_attn_temporal(const float* qkv, const float* Rq, const float* Rk, const float* Rv,
                         const float* mask /* [B][T] or NULL */, float* o, float* attn_out,
                         int B, int T, int P, int C, int heads, void* stream);

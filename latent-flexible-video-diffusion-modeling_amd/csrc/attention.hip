@@ -801,15 +801,21 @@ extern "C" int lfvdm_attn_spatial_bwd(const float* qkv, const float* o, const fl
 
 int lfvdm_attn_temporal2_try(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
                              float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s);
+// (attention_temporal_long.hip) 33 <= T <= 64 frames; LFVDM_E_UNSUPPORTED = head dim not a multiple of 8
+int lfvdm_attn_temporal_long(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
+                             float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s);
+constexpr int TA_MAXT_LONG = 64;
 
 extern "C" int lfvdm_attn_temporal_ring(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask,
                                         float* o, float* attn_out, int B, int T, int P, int C, int heads, const int64_t* rsel_p,
                                         int ring, void* stream) {
-    if (B <= 0 || T <= 0 || T > TA_MAXT || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
+    if (B <= 0 || T <= 0 || T > TA_MAXT_LONG || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
     if (!Rq || !Rk || !Rv || ring < 0 || (ring > 0 && !rsel_p)) return LFVDM_E_SHAPE;
     const RSel rsel = {rsel_p, ring};
     const int F = C / heads;
     hipStream_t s = (hipStream_t)stream;
+    // long windows (33..64 frames): frame-group kernel (attention_temporal_long.hip); T <= 32 below, unchanged
+    if (T > TA_MAXT) return lfvdm_attn_temporal_long(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
     // second-generation kernel (attention_temporal2.hip) for head dims 16 / 32 / 64 and launches that do not fill the chip
     {
         const int rc = lfvdm_attn_temporal2_try(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);

@@ -26,9 +26,15 @@ int lfvdm_attn_temporal2_bwd_rows_try(const float* qkv, const float* dO, const f
                                       const float* mask, float* dqkv, float* Pg, float* dSg, int B, int T, int P, int C, int heads,
                                       hipStream_t s);
 
+// (attention_temporal_long.hip) rows + cols kernels for 33 <= T <= 64 frames; LFVDM_E_UNSUPPORTED = not covered
+int lfvdm_attn_temporal_long_bwd(const float* qkv, const float* d_o, const float* Rq, const float* Rk, const float* Rv,
+                                 const float* mask, float* Pg, float* dSg, float* dqkv, int B, int T, int P, int C, int heads,
+                                 hipStream_t s);
+
 namespace {
 
 constexpr int TB_MAXT = 32;
+constexpr int TB_MAXT_LONG = 64;
 
 template <int TMAX, int FC>
 struct TBStage {
@@ -390,7 +396,8 @@ void attn_temporal_bwd_cols_kernel(const float* __restrict__ qkv, const float* _
 
 // ------------------------------------------------------------------------------------------------ rpe
 // grid (T, heads, B); wave w owns the output tiles (term, f-tile) = w, w + 4, ...; MFMA 16x16x4 with the
-// k index running over pixels.
+// k index running over pixels.  RT = 16-row tiles of the output (2: T <= 32, 4: T <= 64).
+template <int RT>
 __global__ __launch_bounds__(256)
 void attn_temporal_bwd_rpe_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, const float* __restrict__ Pg,
                                   const float* __restrict__ dSg, float* __restrict__ dRq, float* __restrict__ dRk,
@@ -415,34 +422,40 @@ void attn_temporal_bwd_rpe_kernel(const float* __restrict__ qkv, const float* __
         // A operand source: dS row i (term 0), P row i (term 1), dS column i (term 2), element = row index
         const float* Asrc = (term == 1 ? Pg : dSg) + ((size_t)b * P * heads + h) * TT;
         const size_t astride = (size_t)heads * TT;     // per pixel
-        f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        const int row0 = lq, row1 = 16 + lq;
-        const size_t a0 = (term == 2) ? (size_t)row0 * T + i : (size_t)i * T + row0;
-        const size_t a1 = (term == 2) ? (size_t)row1 * T + i : (size_t)i * T + row1;
-        const bool two = T > 16;
-        // 8 k-steps (32 pixels) per iteration: all 24 loads are issued before the first MFMA needs one (the loop is a
-        // chain of dependent-latency loads otherwise)
+        f32x4 acc[RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) acc[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        size_t ar[RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const int row = 16 * rt + lq;
+            ar[rt] = (term == 2) ? (size_t)row * T + i : (size_t)i * T + row;
+        }
+        // 8 k-steps (32 pixels) per iteration: all 8 * (RT + 1) loads are issued before the first MFMA needs one (the
+        // loop is a chain of dependent-latency loads otherwise); row tile rt exists if T > 16 rt
         for (int pb = 0; pb < P; pb += 32) {
-            float bv[8], av0[8], av1[8];
+            float bv[8], av[RT][8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int p = pb + 4 * u + kk;
                 const bool pok = p < P;
                 bv[u] = (pok && colok) ? Bsrc[(size_t)p * bstride] : 0.f;
-                av0[u] = (pok && row0 < T) ? Asrc[(size_t)p * astride + a0] : 0.f;
-                av1[u] = (two && pok && row1 < T) ? Asrc[(size_t)p * astride + a1] : 0.f;
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+                    av[rt][u] = ((rt == 0 || T > 16 * rt) && pok && 16 * rt + lq < T) ? Asrc[(size_t)p * astride + ar[rt]] : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[u], bv[u], acc[0], 0, 0, 0);
-                if (two) acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[u], bv[u], acc[1], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+                    if (rt == 0 || T > 16 * rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][u], bv[u], acc[rt], 0, 0, 0);
             }
         }
         float* out = (term == 0 ? dRk : term == 1 ? dRv : dRq) + ((size_t)(b * T + i) * T) * C + h * F + col;
         const float mul = (term == 1) ? 1.f : scale;
         if (colok) {
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
+            for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = 16 * rt + 4 * kk + r;
@@ -698,17 +711,23 @@ int launch_tb_t(const float* qkv, const float* d_o, const float* Rq, const float
 extern "C" int lfvdm_attn_temporal_bwd(const float* qkv, const float* d_o, const float* Rq, const float* Rk, const float* Rv,
                                        const float* mask, float* ws_p, float* ws_ds, float* dqkv, float* dRq, float* dRk,
                                        float* dRv, int B, int T, int P, int C, int heads, void* stream) {
-    if (B <= 0 || T <= 0 || T > TB_MAXT || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
+    if (B <= 0 || T <= 0 || T > TB_MAXT_LONG || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
     if (!qkv || !d_o || !Rq || !Rk || !Rv || !ws_p || !ws_ds || !dqkv || !dRq || !dRk || !dRv) return LFVDM_E_SHAPE;
     const int F = C / heads;
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if (F % 16 == 0 && T <= 24) rc = launch_tb_t<16>(qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, s);
+    if (T > TB_MAXT) rc = lfvdm_attn_temporal_long_bwd(qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, s);
+    else if (F % 16 == 0 && T <= 24) rc = launch_tb_t<16>(qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, s);
     else if (F % 8 == 0) rc = launch_tb_t<8>(qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, s);
     else return LFVDM_E_UNSUPPORTED;
     if (rc != LFVDM_OK) return rc;
-    hipLaunchKernelGGL(attn_temporal_bwd_rpe_kernel, dim3((unsigned)T, (unsigned)heads, (unsigned)B), dim3(256), 0, s, qkv, d_o,
-                       ws_p, ws_ds, dRq, dRk, dRv, T, P, C, heads);
+    const dim3 grid_rpe((unsigned)T, (unsigned)heads, (unsigned)B);
+    if (T > TB_MAXT)
+        hipLaunchKernelGGL(attn_temporal_bwd_rpe_kernel<4>, grid_rpe, dim3(256), 0, s, qkv, d_o, ws_p, ws_ds, dRq, dRk, dRv, T, P, C,
+                           heads);
+    else
+        hipLaunchKernelGGL(attn_temporal_bwd_rpe_kernel<2>, grid_rpe, dim3(256), 0, s, qkv, d_o, ws_p, ws_ds, dRq, dRk, dRv, T, P, C,
+                           heads);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }

@@ -60,6 +60,7 @@ def chain_local_enabled():
 
 
 CHAIN_MAX_M = int(os.environ.get("LFVDM_CHAIN_MAX_M", "640"))
+MAX_FRAMES = 64       # frames per window of the temporal attention kernels (lfvdm_attn_temporal*)
 CHAIN_TIMEOUT_S = float(os.environ.get("LFVDM_CHAIN_TIMEOUT_S", "2.0"))
 
 
@@ -227,8 +228,9 @@ class Plan:
         m, L = self.model, nat.lib()
         B, T, H, W = self.B, self.T, self.H, self.W
         N = B * T
-        if T > 32:
-            raise RuntimeError("native temporal attention supports at most 32 frames per window")
+        if T > MAX_FRAMES:
+            raise RuntimeError(f"native temporal attention supports at most {MAX_FRAMES} frames per window (got {T}); "
+                               f"use --max_frames {MAX_FRAMES} or less")
         if m.dims != 2:
             raise NotImplementedError("only dims=2 is on the native path (the reference scripts use 2)")
         if not m.use_scale_shift_norm:
