@@ -549,6 +549,26 @@ int lfvdm_conv_out_psample(const float* act, const float* Wp, const float* bias,
                            const float* sqrt_recipm1_acp, const float* coef1, const float* coef2, const float* log_var,
                            int clip, float* sample, float* pred_xstart, float* mean_out, int B, int T, int H, int W, int C,
                            int Cout, const int64_t* seed, void* stream);
+/* DDIM (gaussian_diffusion.py:524-610: ddim_sample, ddim_reverse_sample) as a second update rule of the three update
+ * kernels above, selected at compile time.  With p0 = clamp(sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] eps):
+ *     sample = k1[t] p0 + k2[t] x + [t != 0] sigma[t] z
+ * k1, k2, sigma are per-timestep fp32 tables folded on the host in float64 (GaussianDiffusion.ddim_coefficients; the
+ * reverse step is the same call with the alphas_cumprod_next tables).  sigma == NULL selects the DETERMINISTIC rule
+ * (eta = 0, reverse): noise / noise_in / noise_out / seed are then never read or written and may be NULL, and no random
+ * numbers are generated.  With sigma != NULL the noise stream is lfvdm_p_sample_rng's: the same (seed, t, element) gives
+ * the same z under either rule.  pred_xstart / eps_out / noise_out may be NULL; x and sample may alias. */
+int lfvdm_ddim_sample(const float* x, const float* eps, const float* noise, const int64_t* t, const float* sqrt_recip_acp,
+                      const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
+                      float* sample, float* pred_xstart, int B, int inner, void* stream);
+int lfvdm_ddim_sample_rng(const float* x, const float* eps, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
+                          const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
+                          float* sample, float* pred_xstart, int B, int inner, const int64_t* seed, void* stream);
+/* lfvdm_conv_out_psample with the DDIM rule (same shapes: lfvdm_conv_out_psample_ok). */
+int lfvdm_conv_out_ddim(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
+                        const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
+                        const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
+                        float* sample, float* pred_xstart, int B, int T, int H, int W, int C, int Cout, const int64_t* seed,
+                        void* stream);
 /* Sampler clock of the captured denoising step (the loop `for i in indices: t = th.tensor([i]*B)` of
  * gaussian_diffusion.py:509-512 and _WrappedModel's timestep map, respace.py:117-122, kept on the device):
  * t[b] <- max(t[b] - 1, 0);  model_t[b] <- model_timestep_table[t[b]]. */

@@ -19,7 +19,24 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
 }
 
+// The update rule of the three update kernels below, a COMPILE-TIME choice (the ancestral instantiations are the code they
+// were before the DDIM rules existed):
+//   RULE_ANCESTRAL  mean = c1[t] p0 + c2[t] x, sigma = exp(0.5 logvar[t])                          (:369-401)
+//   RULE_DDIM       the same form with the folded DDIM coefficients k1[t], k2[t] in the c1 / c2 slots and sigma[t] itself
+//                   in the logvar slot (ddim_sample / ddim_reverse_sample, :524-610; folded on the host in float64, see
+//                   GaussianDiffusion.ddim_coefficients)
+//   RULE_DDIM_DET   eta = 0 and the reverse step: no sigma table, no noise read, no Philox rounds, no noise store
+enum { RULE_ANCESTRAL = 0, RULE_DDIM = 1, RULE_DDIM_DET = 2 };
+
+template <int RULE>
+__device__ __forceinline__ float rule_sigma(const float* __restrict__ t_logvar, int64_t tb) {
+    if (RULE == RULE_ANCESTRAL) return tb != 0 ? expf(0.5f * t_logvar[tb]) : 0.f;
+    if (RULE == RULE_DDIM) return tb != 0 ? t_logvar[tb] : 0.f;
+    return 0.f;
+}
+
 // x and sample may alias (the sampler updates its state in place): no __restrict__ on them.
+template <int RULE>
 __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const float* __restrict__ eps,
                                                        const float* __restrict__ noise, const int64_t* __restrict__ t,
                                                        const float* __restrict__ t_recip, const float* __restrict__ t_recipm1,
@@ -31,7 +48,7 @@ __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const flo
     const int64_t tb = t[b];
     const float r = t_recip[tb], rm1 = t_recipm1[tb], c1 = t_c1[tb], c2 = t_c2[tb];
     // sample = mean + [t != 0] * exp(0.5 * log_variance) * noise     (:396-400)
-    const float sigma = tb != 0 ? expf(0.5f * t_logvar[tb]) : 0.f;
+    const float sigma = rule_sigma<RULE>(t_logvar, tb);
     const size_t base = (size_t)b * inner;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += gridDim.x * blockDim.x) {
         const float xv = x[base + i];
@@ -39,7 +56,7 @@ __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const flo
         if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
         const float mean = c1 * p0 + c2 * xv;       // q_posterior_mean_variance (:228-231)
         float sv = mean;
-        if (tb != 0) sv += sigma * noise[base + i];
+        if (RULE != RULE_DDIM_DET && tb != 0) sv += sigma * noise[base + i];
         sample[base + i] = sv;
         if (pred) pred[base + i] = p0;
         if (mean_out) mean_out[base + i] = mean;
@@ -75,6 +92,7 @@ __device__ __forceinline__ f32x4 normal4(unsigned quad, unsigned row, unsigned s
     return (f32x4){m0 * c0, m0 * s0, m1 * c1, m1 * s1};
 }
 
+template <int RULE>
 __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const float* __restrict__ eps,
                                                            float* __restrict__ noise_out, const int64_t* __restrict__ t,
                                                            const float* __restrict__ t_recip, const float* __restrict__ t_recipm1,
@@ -85,13 +103,14 @@ __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const
     const int b = blockIdx.y;
     const int64_t tb = t[b];
     const float r = t_recip[tb], rm1 = t_recipm1[tb], c1 = t_c1[tb], c2 = t_c2[tb];
-    const float sigma = tb != 0 ? expf(0.5f * t_logvar[tb]) : 0.f;
-    const unsigned long long key = (unsigned long long)seed[0];
+    const float sigma = rule_sigma<RULE>(t_logvar, tb);
+    const unsigned long long key = RULE != RULE_DDIM_DET ? (unsigned long long)seed[0] : 0ull;
     const unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
     const size_t base = (size_t)b * inner;
     const int nq = (inner + 3) >> 2;
     for (int qd = blockIdx.x * blockDim.x + threadIdx.x; qd < nq; qd += gridDim.x * blockDim.x) {
-        const f32x4 z = normal4((unsigned)qd, (unsigned)b, (unsigned)tb, k0, k1);
+        f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (RULE != RULE_DDIM_DET) z = normal4((unsigned)qd, (unsigned)b, (unsigned)tb, k0, k1);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int i = 4 * qd + e;
@@ -100,8 +119,8 @@ __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const
                 float p0 = r * xv - rm1 * eps[base + i];
                 if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
                 const float mean = c1 * p0 + c2 * xv;
-                sample[base + i] = mean + sigma * z[e];
-                if (noise_out) noise_out[base + i] = z[e];
+                sample[base + i] = RULE != RULE_DDIM_DET ? mean + sigma * z[e] : mean;
+                if (RULE != RULE_DDIM_DET && noise_out) noise_out[base + i] = z[e];
                 if (pred) pred[base + i] = p0;
                 if (mean_out) mean_out[base + i] = mean;
             }
@@ -125,7 +144,7 @@ struct HeadUpdate {
     int N, T, H, W, C, clip;
 };
 
-template <int CO, int CPL>
+template <int CO, int CPL, int RULE>
 __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate p) {
     extern __shared__ __attribute__((aligned(16))) float wl[];      // [CO * 9][C]
     const int tid = threadIdx.x;
@@ -190,9 +209,10 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
     const size_t at = (size_t)b * inner + i;
     const int64_t tb = p.t[b];
     const float r = p.t_recip[tb], rm1 = p.t_recipm1[tb], c1 = p.t_c1[tb], c2 = p.t_c2[tb];
-    const float sigma = tb != 0 ? expf(0.5f * p.t_logvar[tb]) : 0.f;
-    float z;
-    if (p.noise_in) {
+    const float sigma = rule_sigma<RULE>(p.t_logvar, tb);
+    float z = 0.f;
+    if (RULE == RULE_DDIM_DET) {
+    } else if (p.noise_in) {
         z = p.noise_in[at];
     } else {
         const unsigned long long key = (unsigned long long)p.seed[0];
@@ -203,9 +223,9 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
     float p0 = r * xv - rm1 * e;
     if (p.clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
     const float mean = c1 * p0 + c2 * xv;
-    p.sample[at] = mean + sigma * z;
+    p.sample[at] = RULE != RULE_DDIM_DET ? mean + sigma * z : mean;
     if (p.eps_out) p.eps_out[at] = e;
-    if (p.noise_out) p.noise_out[at] = z;
+    if (RULE != RULE_DDIM_DET && p.noise_out) p.noise_out[at] = z;
     if (p.pred) p.pred[at] = p0;
     if (p.mean_out) p.mean_out[at] = mean;
 }
@@ -339,30 +359,73 @@ extern "C" int lfvdm_sampler_tick(int64_t* t, const float* model_timestep_table,
     return LFVDM_OK;
 }
 
+namespace {
+template <int RULE>
+int launch_update(const float* x, const float* eps, const float* noise, const int64_t* t, const float* recip, const float* recipm1,
+                  const float* c1, const float* c2, const float* sg, int clip, float* sample, float* pred, float* mean_out, int B,
+                  int inner, void* stream) {
+    if (B <= 0 || inner <= 0) return LFVDM_E_SHAPE;
+    int gx = (inner + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(p_sample_kernel<RULE>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise, t, recip, recipm1, c1,
+                       c2, sg, clip, sample, pred, mean_out, inner);
+    LFVDM_CHECK_LAUNCH();
+    return LFVDM_OK;
+}
+
+template <int RULE>
+int launch_update_rng(const float* x, const float* eps, float* noise_out, const int64_t* t, const float* recip,
+                      const float* recipm1, const float* c1, const float* c2, const float* sg, int clip, float* sample, float* pred,
+                      float* mean_out, int B, int inner, const int64_t* seed, void* stream) {
+    if (B <= 0 || inner <= 0 || (RULE != RULE_DDIM_DET && !seed)) return LFVDM_E_SHAPE;
+    int gx = ((inner + 3) / 4 + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(p_sample_rng_kernel<RULE>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise_out, t, recip,
+                       recipm1, c1, c2, sg, clip, sample, pred, mean_out, inner, seed);
+    LFVDM_CHECK_LAUNCH();
+    return LFVDM_OK;
+}
+}  // namespace
+
 extern "C" int lfvdm_p_sample(const float* x, const float* eps, const float* noise, const int64_t* t,
                               const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* coef1,
                               const float* coef2, const float* log_var, int clip, float* sample, float* pred_xstart,
                               float* mean_out, int B, int inner, void* stream) {
-    if (B <= 0 || inner <= 0) return LFVDM_E_SHAPE;
-    int gx = (inner + 255) / 256;
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(p_sample_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise, t, sqrt_recip_acp,
-                       sqrt_recipm1_acp, coef1, coef2, log_var, clip, sample, pred_xstart, mean_out, inner);
-    LFVDM_CHECK_LAUNCH();
-    return LFVDM_OK;
+    return launch_update<RULE_ANCESTRAL>(x, eps, noise, t, sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, log_var, clip, sample,
+                                         pred_xstart, mean_out, B, inner, stream);
 }
 
 extern "C" int lfvdm_p_sample_rng(const float* x, const float* eps, float* noise_out, const int64_t* t,
                                   const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* coef1,
                                   const float* coef2, const float* log_var, int clip, float* sample, float* pred_xstart,
                                   float* mean_out, int B, int inner, const int64_t* seed, void* stream) {
-    if (B <= 0 || inner <= 0 || !seed) return LFVDM_E_SHAPE;
-    int gx = ((inner + 3) / 4 + 255) / 256;
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(p_sample_rng_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise_out, t, sqrt_recip_acp,
-                       sqrt_recipm1_acp, coef1, coef2, log_var, clip, sample, pred_xstart, mean_out, inner, seed);
-    LFVDM_CHECK_LAUNCH();
-    return LFVDM_OK;
+    return launch_update_rng<RULE_ANCESTRAL>(x, eps, noise_out, t, sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, log_var, clip,
+                                             sample, pred_xstart, mean_out, B, inner, seed, stream);
+}
+
+// DDIM: sigma == NULL selects the deterministic rule (eta = 0, and the reverse step): noise / seed are then never read
+extern "C" int lfvdm_ddim_sample(const float* x, const float* eps, const float* noise, const int64_t* t,
+                                 const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* k1, const float* k2,
+                                 const float* sigma, int clip, float* sample, float* pred_xstart, int B, int inner, void* stream) {
+    if (!x || !eps || !t || !sqrt_recip_acp || !sqrt_recipm1_acp || !k1 || !k2 || !sample) return LFVDM_E_SHAPE;
+    if (!sigma)
+        return launch_update<RULE_DDIM_DET>(x, eps, nullptr, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, nullptr, clip, sample,
+                                            pred_xstart, nullptr, B, inner, stream);
+    if (!noise) return LFVDM_E_SHAPE;
+    return launch_update<RULE_DDIM>(x, eps, noise, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, sigma, clip, sample, pred_xstart,
+                                    nullptr, B, inner, stream);
+}
+
+extern "C" int lfvdm_ddim_sample_rng(const float* x, const float* eps, float* noise_out, const int64_t* t,
+                                     const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* k1, const float* k2,
+                                     const float* sigma, int clip, float* sample, float* pred_xstart, int B, int inner,
+                                     const int64_t* seed, void* stream) {
+    if (!x || !eps || !t || !sqrt_recip_acp || !sqrt_recipm1_acp || !k1 || !k2 || !sample) return LFVDM_E_SHAPE;
+    if (!sigma)
+        return launch_update_rng<RULE_DDIM_DET>(x, eps, nullptr, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, nullptr, clip, sample,
+                                                pred_xstart, nullptr, B, inner, nullptr, stream);
+    return launch_update_rng<RULE_DDIM>(x, eps, noise_out, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, sigma, clip, sample,
+                                        pred_xstart, nullptr, B, inner, seed, stream);
 }
 
 extern "C" int lfvdm_conv_out_psample_ok(int N, int H, int W, int C, int Cout) {
@@ -372,20 +435,16 @@ extern "C" int lfvdm_conv_out_psample_ok(int N, int H, int W, int C, int Cout) {
     return LFVDM_OK;
 }
 
-extern "C" int lfvdm_conv_out_psample(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
-                                      const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
-                                      const float* sqrt_recipm1_acp, const float* coef1, const float* coef2,
-                                      const float* log_var, int clip, float* sample, float* pred_xstart, float* mean_out,
-                                      int B, int T, int H, int W, int C, int Cout, const int64_t* seed, void* stream) {
-    if (B <= 0 || T <= 0 || !act || !Wp || !bias || !x || !sample || !t || (!noise_in && !seed)) return LFVDM_E_SHAPE;
-    if (int rc = lfvdm_conv_out_psample_ok(B * T, H, W, C, Cout)) return rc;
-    const HeadUpdate p = {act, Wp, bias, x, noise_in, eps_out, noise_out, sample, pred_xstart, mean_out, t, seed, sqrt_recip_acp,
-                          sqrt_recipm1_acp, coef1, coef2, log_var, B * T, T, H, W, C, clip};
-    const long quads = (long)B * T * H * (W / 4);
+namespace {
+template <int RULE>
+int launch_head(const HeadUpdate& p, int Cout, void* stream) {
+    if (int rc = lfvdm_conv_out_psample_ok(p.N, p.H, p.W, p.C, Cout)) return rc;
+    const long quads = (long)p.N * p.H * (p.W / 4);
     const dim3 grid((unsigned)((quads + 3) / 4));
-    const size_t lds = (size_t)Cout * 9 * C * sizeof(float);
+    const size_t lds = (size_t)Cout * 9 * p.C * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define LFVDM_HEAD(CO, CPL) hipLaunchKernelGGL((conv_out_psample_kernel<CO, CPL>), grid, dim3(256), lds, s, p)
+    const int C = p.C;
+#define LFVDM_HEAD(CO, CPL) hipLaunchKernelGGL((conv_out_psample_kernel<CO, CPL, RULE>), grid, dim3(256), lds, s, p)
     if (Cout == 4) {
         if (C == 64) LFVDM_HEAD(4, 1); else if (C == 128) LFVDM_HEAD(4, 2); else LFVDM_HEAD(4, 4);
     } else {
@@ -394,6 +453,33 @@ extern "C" int lfvdm_conv_out_psample(const float* act, const float* Wp, const f
 #undef LFVDM_HEAD
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
+}
+}  // namespace
+
+extern "C" int lfvdm_conv_out_psample(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
+                                      const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
+                                      const float* sqrt_recipm1_acp, const float* coef1, const float* coef2,
+                                      const float* log_var, int clip, float* sample, float* pred_xstart, float* mean_out,
+                                      int B, int T, int H, int W, int C, int Cout, const int64_t* seed, void* stream) {
+    if (B <= 0 || T <= 0 || !act || !Wp || !bias || !x || !sample || !t || (!noise_in && !seed)) return LFVDM_E_SHAPE;
+    const HeadUpdate p = {act, Wp, bias, x, noise_in, eps_out, noise_out, sample, pred_xstart, mean_out, t, seed, sqrt_recip_acp,
+                          sqrt_recipm1_acp, coef1, coef2, log_var, B * T, T, H, W, C, clip};
+    return launch_head<RULE_ANCESTRAL>(p, Cout, stream);
+}
+
+// the DDIM rules in the same launch; sigma == NULL: deterministic (noise_in / noise_out / seed are never touched)
+extern "C" int lfvdm_conv_out_ddim(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
+                                   const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
+                                   const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
+                                   float* sample, float* pred_xstart, int B, int T, int H, int W, int C, int Cout,
+                                   const int64_t* seed, void* stream) {
+    if (B <= 0 || T <= 0 || !act || !Wp || !bias || !x || !sample || !t || !sqrt_recip_acp || !sqrt_recipm1_acp || !k1 || !k2)
+        return LFVDM_E_SHAPE;
+    if (sigma && !noise_in && !seed) return LFVDM_E_SHAPE;
+    const HeadUpdate p = {act, Wp, bias, x, sigma ? noise_in : nullptr, eps_out, sigma ? noise_out : nullptr, sample, pred_xstart,
+                          nullptr, t, sigma ? seed : nullptr, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, sigma, B * T, T, H, W, C,
+                          clip};
+    return sigma ? launch_head<RULE_DDIM>(p, Cout, stream) : launch_head<RULE_DDIM_DET>(p, Cout, stream);
 }
 
 extern "C" int lfvdm_masked_mse(const float* a, const float* b, const float* mask, float* out, int B, int T,

@@ -131,6 +131,9 @@ _SIGS = {
     "lfvdm_p_sample_rng": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp], c_i),
     "lfvdm_conv_out_psample_ok": ([c_i] * 5, c_i),
     "lfvdm_conv_out_psample": ([c_fp] * 13 + [c_i, c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp], c_i),
+    "lfvdm_ddim_sample": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
+    "lfvdm_ddim_sample_rng": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_i, c_i, c_fp, c_fp], c_i),
+    "lfvdm_conv_out_ddim": ([c_fp] * 13 + [c_i, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp], c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_bwd_stats": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp], c_i),
     "lfvdm_gn_bwd_apply": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
@@ -663,6 +666,31 @@ def conv_out_psample(act, wp, bias, eps_out, x, noise_in, noise_out, t, recip, r
                                        int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B, T, H, W, act.shape[-1], Cout,
                                        ptr(seed, torch.int64) if seed is not None else None, stream()),
           "lfvdm_conv_out_psample")
+
+
+def ddim_sample(x, eps, noise, t, recip, recipm1, k1, k2, sigma, clip, sample, pred=None):
+    """The DDIM update with given noise (lfvdm_ddim_sample); ``sigma=None``: the deterministic rule, ``noise`` is not read."""
+    B = x.shape[0]
+    check(lib().lfvdm_ddim_sample(ptr(x), ptr(eps), ptr(noise), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1), ptr(k2),
+                                  ptr(sigma), int(bool(clip)), ptr(sample), ptr(pred), B, x.numel() // B, stream()),
+          "lfvdm_ddim_sample")
+
+
+def ddim_sample_rng(x, eps, noise_out, t, recip, recipm1, k1, k2, sigma, clip, sample, seed, pred=None):
+    """The DDIM update with the noise drawn in the kernel (lfvdm_p_sample_rng's stream); ``sigma=None``: no noise at all."""
+    B = x.shape[0]
+    check(lib().lfvdm_ddim_sample_rng(ptr(x), ptr(eps), ptr(noise_out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1),
+                                      ptr(k2), ptr(sigma), int(bool(clip)), ptr(sample), ptr(pred), B, x.numel() // B,
+                                      ptr(seed, torch.int64) if seed is not None else None, stream()), "lfvdm_ddim_sample_rng")
+
+
+def conv_out_ddim(act, wp, bias, eps_out, x, noise_in, noise_out, t, recip, recipm1, k1, k2, sigma, clip, sample, seed, pred=None):
+    """The U-Net's output conv and the DDIM update in one launch (lfvdm_conv_out_ddim); layouts as conv_out_psample."""
+    B, T, Cout, H, W = x.shape
+    check(lib().lfvdm_conv_out_ddim(ptr(act), ptr(wp), ptr(bias), ptr(eps_out), ptr(x), ptr(noise_in), ptr(noise_out),
+                                    ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1), ptr(k2), ptr(sigma), int(bool(clip)),
+                                    ptr(sample), ptr(pred), B, T, H, W, act.shape[-1], Cout,
+                                    ptr(seed, torch.int64) if seed is not None else None, stream()), "lfvdm_conv_out_ddim")
 
 
 def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):

@@ -6,9 +6,12 @@ What is native here
   * ``q_sample``, the fused x0-hat / clamp / posterior-mean / noise-add update of ``p_sample`` and the
     masked MSE are single HIP kernels (csrc/diffusion_ops.hip);
   * ``p_sample_loop`` replays ONE captured hipGraph per denoising step (timestep remap + U-Net
-    forward + noise draw + update + t decrement): no host work inside the 1000-step loop.
+    forward + noise draw + update + t decrement): no host work inside the 1000-step loop;
+  * DDIM (``ddim_sample``, ``ddim_reverse_sample``, ``ddim_sample_loop[_progressive]``, reference :524-685) is a second
+    update rule of the same kernels and of the same replayed step; its per-timestep coefficients are folded on the host in
+    float64 (``ddim_coefficients``).
 
-Out of scope (not reached by the default CLIs): learned-sigma / KL losses, DDIM,
+Out of scope (not reached by the default CLIs): learned-sigma / KL losses,
 bits-per-dim loops, the VAE (needs a network fetch) — they raise NotImplementedError.
 """
 import enum
@@ -103,6 +106,7 @@ class GaussianDiffusion:
             self.pre_encoded_stats_dict["std"] = self.pre_encoded_stats_dict["std"].reshape(1, 1, -1, 1, 1)
         self.original_dtype = None
         self._dev_cache = {}
+        self._ddim_cache = {}
         self._samplers = {}
         self.setup_enc_dec()
 
@@ -131,6 +135,47 @@ class GaussianDiffusion:
                 tb["model_variance"] = th.from_numpy(v).float().to(device)
                 tb["model_log_variance"] = th.from_numpy(lv).float().to(device)
             self._dev_cache[key] = tb
+        return tb
+
+    def ddim_coefficients(self, eta=0.0, reverse=False):
+        """float64 per-timestep tables {"k1", "k2", "sigma"} of the DDIM update (reference :524-610) in the folded form
+        the kernels evaluate:  sample = k1[t] * p0 + k2[t] * x + [t != 0] * sigma[t] * z.
+
+        The reference computes eps' = (sqrt_recip_acp x - p0) / sqrt_recipm1_acp and then
+        sqrt(abar_prev) p0 + sqrt(1 - abar_prev - sigma^2) eps'; substituting eps' gives
+        k1 = sqrt(abar_prev) - c / sqrt_recipm1_acp and k2 = c * sqrt_recip_acp / sqrt_recipm1_acp with
+        c = sqrt(1 - abar_prev - sigma^2).  Folding keeps the division by sqrt_recipm1_acp (0.01 at t = 0 of a strided
+        chain) out of fp32: there c is exactly 0, so k1 = 1, k2 = 0 and the last sample IS pred_xstart.
+        ``reverse``: the encoding step towards t + 1 (eta = 0 only), abar_next in place of abar_prev."""
+        eta = float(eta)
+        key = (eta, bool(reverse))
+        co = self._ddim_cache.get(key)
+        if co is None:
+            abar = self.alphas_cumprod
+            r, rm1 = self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod
+            if reverse:
+                assert eta == 0.0, "Reverse ODE only for deterministic path"
+                to = self.alphas_cumprod_next
+                sigma = np.zeros_like(abar)
+            else:
+                to = self.alphas_cumprod_prev
+                sigma = eta * np.sqrt((1 - to) / (1 - abar)) * np.sqrt(1 - abar / to)
+            c = np.sqrt(1 - to - sigma ** 2)
+            co = {"k1": np.sqrt(to) - c / rm1, "k2": c * r / rm1, "sigma": sigma}
+            self._ddim_cache[key] = co
+        return co
+
+    def ddim_tables(self, device, eta=0.0, reverse=False):
+        """fp32 device copies of ``ddim_coefficients``, uploaded once per (device, eta, direction).  ``sigma`` is None for
+        eta = 0 and for the reverse step: the kernels then run their deterministic instantiation."""
+        eta = float(eta)
+        key = (str(device), eta, bool(reverse))
+        tb = self._ddim_cache.get(key)
+        if tb is None:
+            co = self.ddim_coefficients(eta, reverse)
+            tb = {n: th.from_numpy(co[n]).float().to(device) for n in ("k1", "k2")}
+            tb["sigma"] = th.from_numpy(co["sigma"]).float().to(device) if eta != 0.0 and not reverse else None
+            self._ddim_cache[key] = tb
         return tb
 
     def _gather(self, name, t, ndim):
@@ -335,14 +380,132 @@ class GaussianDiffusion:
             yield out
             img = out["sample"]
 
-    def _graph_sampler(self, unet, shape, clip_denoised):
-        key = (id(unet), shape, bool(clip_denoised))
+    # ------------------------------------------------------------------ DDIM (reference :524-685)
+    def _ddim_update(self, x, eps, t, noise, clip_denoised, eta, reverse=False):
+        tb, co = self.tables(x.device), self.ddim_tables(x.device, eta, reverse)
+        sample = th.empty_like(x, memory_format=th.contiguous_format)
+        pred = th.empty_like(sample)
+        nat.ddim_sample(x.contiguous(), eps.contiguous(), noise.contiguous() if co["sigma"] is not None else None,
+                        t.to(th.int64).contiguous(), tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"],
+                        co["k1"], co["k2"], co["sigma"], clip_denoised, sample, pred)
+        return sample, pred
+
+    def _ddim_update_denoised(self, x, eps, t, noise, clip_denoised, denoised_fn, eta, reverse=False):
+        """The two-launch route of ``_p_update_denoised`` for DDIM: x0-hat, the user's function, the clamp, then the folded
+        rule as elementwise device ops."""
+        n = x.dim()
+        pred = denoised_fn(self._predict_xstart_from_eps(x, t, eps))
+        if clip_denoised:
+            pred = pred.clamp(-1, 1)
+        co = self.ddim_tables(x.device, eta, reverse)
+        sample = _bshape(co["k1"][t], n) * pred + _bshape(co["k2"][t], n) * x
+        if co["sigma"] is not None:
+            sample = sample + _bshape((t != 0).to(x.dtype) * co["sigma"][t], n) * noise
+        return sample, pred
+
+    def _ddim_step(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, reverse, noise=None):
+        self._check_native_modes()
+        model_kwargs = model_kwargs or {}
+        assert t.shape == (x.shape[0],)
+        eps, _ = model(x, self._scale_timesteps(t), return_attn_weights=False, **model_kwargs)
+        if float(eta) != 0.0 and noise is None:
+            noise = th.randn_like(x)
+        if denoised_fn is not None:
+            sample, pred = self._ddim_update_denoised(x, eps, t, noise, clip_denoised, denoised_fn, eta, reverse)
+        else:
+            sample, pred = self._ddim_update(x, eps, t, noise, clip_denoised, eta, reverse)
+        return {"sample": sample, "pred_xstart": pred}
+
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, noise=None):
+        """x_{t-1} from the model using DDIM (reference :524-571); same usage as ``p_sample``.  eta = 0 draws no noise at
+        all (the reference draws it and multiplies it by 0); ``noise`` (extension, as in ``p_sample``) injects the N(0,1)
+        draw used when eta > 0."""
+        return self._ddim_step(model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, False, noise)
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """x_{t+1} from the model using the DDIM reverse ODE (reference :573-610)."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        return self._ddim_step(model, x, t, clip_denoised, denoised_fn, model_kwargs, 0.0, True)
+
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None, device=None,
+                         progress=False, eta=0.0, latent_mask=None, return_decoded=True):
+        """Full DDIM chain (reference :612-642) -> the final sample tensor alone (no attention summary).
+
+        Extension: ``latent_mask`` and ``return_decoded`` are accepted and the final sample is treated as ``p_sample_loop``
+        treats it (decoded unless ``return_decoded=False``; refused before the chain runs when there is nothing to decode
+        with), so that the long-video sampler can call either loop.  The reference's DDIM loop returns the raw sample."""
+        if return_decoded and not self.can_decode():
+            raise NotImplementedError("ddim_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); pass "
+                                      "return_decoded=False for latents - refused BEFORE the chain runs")
+        final = None
+        for sample in self._ddim_loop(model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress, eta,
+                                      _reuse_buffers=True, _final_only=True):
+            final = sample
+        out = final["sample"].clone()
+        return self.decode(out) if return_decoded else out
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                     device=None, progress=False, eta=0.0):
+        """Generator over the dicts of ``ddim_sample`` for t = T-1 .. 0 (reference :644-685); replayed through
+        ``GraphSampler`` under the conditions of ``p_sample_loop_progressive``."""
+        return self._ddim_loop(model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress, eta)
+
+    def _ddim_loop(self, model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress, eta,
+                   _reuse_buffers=False, _final_only=False):
+        from .unet import UNetVideoModel
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        img = noise if noise is not None else th.randn(*shape, device=device)
+        indices = list(range(self.num_timesteps))[::-1]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        inner = getattr(model, "model", model)  # _WrappedModel -> module
+        inner = getattr(inner, "module", inner)  # DDP -> module
+        fast = isinstance(inner, UNetVideoModel) and img.is_cuda and denoised_fn is None and model_kwargs is not None
+        if fast:
+            sampler = self._graph_sampler(inner, tuple(shape), clip_denoised, rule=("ddim", float(eta)))
+            sampler.begin(img, model_kwargs)
+            if _final_only and not progress:
+                out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
+                if sampler.chain_timed_out():     # as p_sample_loop: the samples are garbage -> one launch per stage, again
+                    sampler.fall_back()
+                    sampler.begin(img, model_kwargs)
+                    out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
+                yield {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
+                return
+            for n, i in enumerate(indices):
+                out = sampler.step(i)
+                if (n & 63) == 63 or i == 0:      # see p_sample_loop_progressive
+                    if sampler.chain_timed_out():
+                        sampler.fall_back()
+                        raise RuntimeError("a persistent level chain timed out during this sampling chain (lfvdm_level_chain): "
+                                           "the states yielded since the last check are not valid; the plan now runs one "
+                                           "launch per stage - run the chain again")
+                yield {k: (out[k] if _reuse_buffers else out[k].clone()) for k in ("sample", "pred_xstart")}
+            return
+        for i in indices:
+            t = th.full((shape[0],), i, device=device, dtype=th.long)
+            with th.no_grad():
+                out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                       model_kwargs=model_kwargs, eta=eta)
+            yield out
+            img = out["sample"]
+
+    def _graph_sampler(self, unet, shape, clip_denoised, rule=("ancestral",)):
+        # the update rule is part of the key (appended: position 1 stays the shape): a DDIM chain and an ancestral chain on
+        # the same shape never share a captured graph
+        key = (id(unet), shape, bool(clip_denoised), tuple(rule))
         s = self._samplers.get(key)
         if s is None or s.unet is not unet or s.engine is not unet.native_engine():
-            s = GraphSampler(self, unet, shape, clip_denoised)
+            s = GraphSampler(self, unet, shape, clip_denoised, rule=rule)
             self._samplers.pop(key, None)
-            while len(self._samplers) >= 4:   # graphs pin device memory: keep the few window shapes of a
-                self._samplers.pop(next(iter(self._samplers)))   # long-video schedule (K, K-1, tail)
+            # graphs pin device memory: keep the few window shapes of a long-video schedule (K, K-1, tail).  DDIM samplers
+            # count against the SAME four: the limit bounds pinned memory, which does not care about the rule, and a
+            # long-video run uses one rule throughout
+            while len(self._samplers) >= 4:
+                self._samplers.pop(next(iter(self._samplers)))
         else:
             self._samplers.pop(key)           # re-insert: most recently used last
         self._samplers[key] = s
@@ -473,12 +636,17 @@ class GraphSampler:
     """One denoising step (timestep remap -> U-Net forward -> noise -> x_{t-1} update -> t -= 1)
     captured as a hipGraph over the engine's static buffers; ``step`` is a single replay."""
 
-    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False):
+    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False, rule=("ancestral",)):
         # inject_noise (parity tests): the replayed step READS ``self.noise`` - the caller fills it before every
         # ``step`` - instead of drawing it (the reference's th.randn_like, gaussian_diffusion.py:396)
+        # rule: ("ancestral",) or ("ddim", eta) - which update closes the step; fixed for the life of the captured graphs
         self.diffusion, self.unet, self.shape = diffusion, unet, tuple(shape)
         self.clip = bool(clip_denoised)
         self.inject_noise = bool(inject_noise)
+        self.rule = tuple(rule)
+        if self.rule[0] not in ("ancestral", "ddim") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
+            raise ValueError(f"unknown update rule {rule!r}")
+        self.ddim = None                # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic)
         B, T, Cx, H, W = self.shape
         from ._engine import Plan
         # a private plan: the sampler's state lives in its static buffers, so it must not be shared
@@ -490,6 +658,8 @@ class GraphSampler:
         self.plan.refresh_weights()
         dev = self.plan.dev
         self.tb = diffusion.tables(dev)
+        if self.rule[0] == "ddim":
+            self.ddim = diffusion.ddim_tables(dev, self.rule[1])
         self.ts_table = diffusion.model_timestep_table(dev)
         self.t_buf = self.plan.t_sel if self.plan.time_steps else th.zeros(B, dtype=th.int64, device=dev)
         self._table_events = None      # (start, end) events around the table build of the last begin()
@@ -529,9 +699,12 @@ class GraphSampler:
 
         # the x_{t-1} update rides in the plan's last launch (output conv + update: lfvdm_conv_out_psample) where the
         # shape allows; LFVDM_FUSED_HEAD=0 keeps the two launches (A/B aid)
+        dd = self.ddim
+        det = dd is not None and dd["sigma"] is None       # eta = 0: no noise of any kind, whatever the noise settings say
         fused = (os.environ.get("LFVDM_FUSED_HEAD", "1") != "0"
-                 and (self.inject_noise or os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
-                 and pl.fuse_head_update(self.t_buf, tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise))
+                 and (det or self.inject_noise or os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
+                 and pl.fuse_head_update(self.t_buf, tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
+                                         ddim=dd))
         if pl.time_steps and os.environ.get("LFVDM_TICK_IN_CONV", "1") != "0":
             pl.launch(tick=(self.t_buf, self.ts_table))      # the clock rides in the first launch of the forward
             self.extra_launches = 1                           # (the update; bench.py reports launches per step)
@@ -541,6 +714,18 @@ class GraphSampler:
             self.extra_launches = 2
         if fused:
             self.extra_launches -= 1
+            return
+        if dd is not None:
+            recip, recipm1 = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
+            if det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch"):
+                nat.ddim_sample_rng(pl.x_in, pl.out, None if det else self.noise, self.t_buf, recip, recipm1, dd["k1"], dd["k2"],
+                                    dd["sigma"], self.clip, pl.x_in, None if det else self.seed, self.pred)
+                return
+            if not self.inject_noise:
+                self.extra_launches = getattr(self, "extra_launches", 2) + 1
+                self.noise.normal_()
+            nat.ddim_sample(pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, dd["k1"], dd["k2"], dd["sigma"], self.clip,
+                            pl.x_in, self.pred)
             return
         if not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch":
             nat.p_sample_rng(pl.x_in, pl.out, self.noise, self.t_buf, tb["sqrt_recip_alphas_cumprod"],

@@ -58,6 +58,12 @@ class SpacedDiffusion(GaussianDiffusion):
     def p_sample(self, model, *args, **kwargs):
         return super().p_sample(self._wrap_model(model), *args, **kwargs)
 
+    def ddim_sample(self, model, *args, **kwargs):
+        return super().ddim_sample(self._wrap_model(model), *args, **kwargs)
+
+    def ddim_reverse_sample(self, model, *args, **kwargs):
+        return super().ddim_reverse_sample(self._wrap_model(model), *args, **kwargs)
+
     def _wrap_model(self, model):
         if isinstance(model, _WrappedModel):
             return model
