@@ -925,7 +925,7 @@ extern "C" int lfvdm_gn_bwd_ws(const float* da, const float* src0, const float* 
 static int gn_temporal_bwd_impl(const float* x, const float* dy, const float* gamma, float eps, float* dx, float* dgamma,
                                float* dbeta, int B, int T, int P, int C, int accumulate, float* det_ws, long det_ws_floats,
                                hipStream_t s) {
-    if (B <= 0 || T <= 0 || P <= 0 || C % 32 || C > GTB_MAXC) return LFVDM_E_SHAPE;
+    if (B <= 0 || T <= 0 || P <= 0 || C <= 0 || C % 32 || C > GTB_MAXC) return LFVDM_E_SHAPE;
     const long samples = (long)B * P;
     const int Q = C / 4;
     const long nwg = (samples + 3) / 4;

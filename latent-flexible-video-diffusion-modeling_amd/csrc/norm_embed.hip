@@ -1096,7 +1096,7 @@ extern "C" int lfvdm_gn_coef(const float* src0, const float* src1, int C0, int C
 
 extern "C" int lfvdm_gn_temporal(const float* x, const float* gamma, const float* beta, float eps, float* y, int B, int T,
                                  int P, int C, void* stream) {
-    if (B <= 0 || T <= 0 || P <= 0 || C % 32 || C > GT_MAXC) return LFVDM_E_SHAPE;
+    if (B <= 0 || T <= 0 || P <= 0 || C <= 0 || C % 32 || C > GT_MAXC) return LFVDM_E_SHAPE;
     const long samples = (long)B * P;
     const dim3 grid((unsigned)((samples + 3) / 4));
     const int Q = C / 4;

@@ -158,6 +158,16 @@ def _pack_t(w4, ld=0):
     return _packs.get(w4, True, ld)
 
 
+def _rows(t):
+    """(pointer, row stride) of an optional [M][>= C] row view (None -> (NULL, 0)).  The kernels read such rows as float4
+    with their own row stride, so a column slice of a wider buffer is fine: unit column stride, 16-byte aligned rows."""
+    if t is None:
+        return None, 0
+    if not t.is_cuda or t.dtype != th.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        raise RuntimeError("expected float32 device rows with unit column stride and 16-byte aligned rows")
+    return t.data_ptr(), t.stride(0)
+
+
 def _grad_of(p):
     """The parameter's gradient buffer (the arena view set up by TrainLoop, or a fresh zero tensor)."""
     if p.grad is None:
@@ -460,6 +470,7 @@ def _gn_backward(da, a, b, C0, C1, N, P, cA, cB, stats, act, gamma, beta, film, 
     C = C0 + C1
     if add2 is not None and not inplace:
         add, add2 = (add2 if add is None else add + add2), None
+    (p_add, ld_add), (p_add2, ld_add2) = _rows(add), _rows(add2)
     L = nat.lib()
     dxa = _new(N * P, C0, like=da)
     dxb = _new(N * P, C1, like=da) if C1 else None
@@ -474,8 +485,7 @@ def _gn_backward(da, a, b, C0, C1, N, P, cA, cB, stats, act, gamma, beta, film, 
         # (the statistics + dx launch is the training path's fused kernel, with the sums stored instead of added)
         sums = _new(N, C, 2, like=da)
         nat.check(L.lfvdm_gn_bwd_fused_sums(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
-                                            act, nat.ptr(dxa), nat.ptr(dxb), nat.ptr(add), add.stride(0) if add is not None else 0,
-                                            nat.ptr(add2), add2.stride(0) if add2 is not None else 0, nat.ptr(sums), nat.stream()),
+                                            act, nat.ptr(dxa), nat.ptr(dxb), p_add, ld_add, p_add2, ld_add2, nat.ptr(sums), nat.stream()),
                   "lfvdm_gn_bwd_fused_sums")
         dfilm = None
         if film is not None:
@@ -495,8 +505,7 @@ def _gn_backward(da, a, b, C0, C1, N, P, cA, cB, stats, act, gamma, beta, film, 
             nat.ptr(dxa), nat.ptr(dxb), nat.ptr(gamma), nat.ptr(beta),
             film.data_ptr() if film is not None else None, film.stride(0) if film is not None else 0, T,
             nat.ptr(_grad_of(gamma)), nat.ptr(_grad_of(beta)), dfilm.data_ptr() if dfilm is not None else None,
-            dfilm.stride(0) if dfilm is not None else 0, nat.ptr(add), add.stride(0) if add is not None else 0,
-            nat.ptr(add2), add2.stride(0) if add2 is not None else 0, nat.stream()), "lfvdm_gn_bwd_fused")
+            dfilm.stride(0) if dfilm is not None else 0, p_add, ld_add, p_add2, ld_add2, nat.stream()), "lfvdm_gn_bwd_fused")
         return dxa, dxb, None, None, (None if dfilm_out is not None else dfilm)
     sums = _new(N, C, 2, like=da)
     nat.check(L.lfvdm_gn_bwd_stats(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
@@ -527,13 +536,13 @@ def _gn_backward_chunked(da, a, b, C0, C1, N, P, cA, cB, stats, act, gamma, beta
         dfilm = dfilm_out if dfilm_out is not None else th.zeros(N // T, 2 * C, device=da.device, dtype=th.float32)
     fptr = film.data_ptr() if film is not None else None
     fld = film.stride(0) if film is not None else 0
+    (p_add, ld_add), (p_add2, ld_add2) = _rows(add), _rows(add2)
     nat.check(L.lfvdm_gn_bwd_ws(
         nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats), act, nat.ptr(dxa),
         nat.ptr(dxb), nat.ptr(gamma), nat.ptr(beta), fptr if atomics else None, fld, T,
         nat.ptr(_grad_of(gamma)) if atomics else None, nat.ptr(_grad_of(beta)) if atomics else None,
         dfilm.data_ptr() if (atomics and dfilm is not None) else None, dfilm.stride(0) if dfilm is not None else 0,
-        nat.ptr(add), add.stride(0) if add is not None else 0, nat.ptr(add2), add2.stride(0) if add2 is not None else 0,
-        nat.ptr(sums), nat.ptr(ws), need, nat.stream()), "lfvdm_gn_bwd_ws")
+        p_add, ld_add, p_add2, ld_add2, nat.ptr(sums), nat.ptr(ws), need, nat.stream()), "lfvdm_gn_bwd_ws")
     if atomics:
         return dxa, dxb, None, None, (None if dfilm_out is not None else dfilm)
     if inplace:

@@ -166,10 +166,14 @@ def test_distributed_data_parallel_wrap_fires_hooks_and_matches_plain_gradients(
         assert torch.allclose(p.grad, q.grad, rtol=1e-4, atol=1e-4 * float(q.grad.abs().max()) + 1e-4 * gmax), k
 
 
-def test_grouped_rpe_training_path_matches_per_network_path(monkeypatch):
+@pytest.mark.parametrize("deterministic", ["0", "1"], ids=["atomics", "deterministic"])
+def test_grouped_rpe_training_path_matches_per_network_path(deterministic, monkeypatch):
     """T*T >= 32: the RPE networks of a training step run as grouped launches (lfvdm_rpe_nets with stored activations,
     lfvdm_rpe_nets_bwd, lfvdm_conv_wgrad_grouped).  Every parameter gradient must agree with the per-network path
-    (itself pinned to the oracle above), and with the oracle's gradients for the RPE parameters."""
+    (itself pinned to the oracle above), and with the oracle's gradients for the RPE parameters.  With
+    LFVDM_DETERMINISTIC=1 the grouped backward is lfvdm_rpe_nets_bwd_det: a second grouped step gives bitwise the same
+    gradients."""
+    monkeypatch.setenv("LFVDM_DETERMINISTIC", deterministic)
     cfg, sd, _ = load_case("micro")
     B, T, C, H = 2, 8, cfg["in_channels"], 16
     g = torch.Generator().manual_seed(11)
@@ -181,16 +185,19 @@ def test_grouped_rpe_training_path_matches_per_network_path(monkeypatch):
     probe = torch.randn(B, T, cfg["out_channels"], H, H, generator=g)
     d = dict(x=x.cuda(), x0=x0.cuda(), t=t.cuda(), fi=fi.cuda(), obs=obs.cuda(), lat=lat.cuda())
     grads = {}
-    for mode in ("1", "0"):
-        monkeypatch.setenv("LFVDM_RPE_GROUPED", mode)
+    for mode in ("1", "0") + (("1 again",) if deterministic == "1" else ()):
+        monkeypatch.setenv("LFVDM_RPE_GROUPED", mode[0])
         model = build_native(cfg, sd).train()
         model.native_grad_accumulation = True
         out, _ = model(d["x"], x0=d["x0"], timesteps=d["t"], frame_indices=d["fi"], obs_mask=d["obs"], latent_mask=d["lat"])
         (out * probe.cuda()).sum().backward()
         grads[mode] = {k: p.grad.clone() for k, p in model.named_parameters()}
-        if mode == "1":
+        if mode[0] == "1":
             from improved_diffusion import _backward as bw
             assert bw._rpe_group.state is not None, "the grouped path should have been taken"
+    if deterministic == "1":
+        diff = [k for k in grads["1"] if not torch.equal(grads["1"][k], grads["1 again"][k])]
+        assert not diff, f"grouped deterministic step not bitwise repeatable: {diff[:5]}"
     gmax = max(float(v.abs().max()) for v in grads["0"].values())
     for k in grads["0"]:
         a, b = grads["1"][k], grads["0"][k]
