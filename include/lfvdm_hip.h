@@ -569,6 +569,33 @@ int lfvdm_conv_out_ddim(const float* act, const float* Wp, const float* bias, fl
                         const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
                         float* sample, float* pred_xstart, int B, int T, int H, int W, int C, int Cout, const int64_t* seed,
                         void* stream);
+/* x0-prediction models (predict_xstart=True, ModelMeanType.START_X, gaussian_diffusion.py:305-326): what the network
+ * returns is a second COMPILE-TIME property of the same three kernels.  The three entries below carry it next to the
+ * rule and dispatch over the 3 rules x 2 mean types; the six entries above keep their signatures and their code.
+ *   mean_type LFVDM_MEAN_X0:  p0 = clamp(model_out) - sqrt_recip_acp / sqrt_recipm1_acp are never read and may be NULL
+ *   mean_type LFVDM_MEAN_EPS: p0 = clamp(sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] model_out), as above
+ *   rule LFVDM_RULE_ANCESTRAL: c1 / c2 = posterior_mean_coef1 / 2, sg = the log-variance table (required)
+ *   rule LFVDM_RULE_DDIM:      c1 / c2 = k1 / k2, sg = sigma, or NULL for the deterministic rule (no noise, no seed)
+ * then sample = c1[t] p0 + c2[t] x + [t != 0] sigma z for either mean type, with the same noise stream (the same
+ * (seed, t, element) gives the same z).  An unknown rule or mean_type -> LFVDM_E_SHAPE.  pred_xstart / mean_out /
+ * noise_out / out (the convolution's result) may be NULL; x and sample may alias.  Shapes of the fused launch:
+ * lfvdm_conv_out_psample_ok. */
+#define LFVDM_RULE_ANCESTRAL 0
+#define LFVDM_RULE_DDIM 1
+#define LFVDM_MEAN_EPS 0
+#define LFVDM_MEAN_X0 1
+int lfvdm_update_x0(const float* x, const float* model_out, const float* noise, const int64_t* t, const float* sqrt_recip_acp,
+                    const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg, int rule, int mean_type,
+                    int clip, float* sample, float* pred_xstart, float* mean_out, int B, int inner, void* stream);
+int lfvdm_update_rng_x0(const float* x, const float* model_out, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
+                        const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg, int rule,
+                        int mean_type, int clip, float* sample, float* pred_xstart, float* mean_out, int B, int inner,
+                        const int64_t* seed, void* stream);
+int lfvdm_conv_out_update_x0(const float* act, const float* Wp, const float* bias, float* out, const float* x,
+                             const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
+                             const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg, int rule,
+                             int mean_type, int clip, float* sample, float* pred_xstart, float* mean_out, int B, int T, int H,
+                             int W, int C, int Cout, const int64_t* seed, void* stream);
 /* Sampler clock of the captured denoising step (the loop `for i in indices: t = th.tensor([i]*B)` of
  * gaussian_diffusion.py:509-512 and _WrappedModel's timestep map, respace.py:117-122, kept on the device):
  * t[b] <- max(t[b] - 1, 0);  model_t[b] <- model_timestep_table[t[b]]. */

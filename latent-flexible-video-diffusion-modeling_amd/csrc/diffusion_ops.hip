@@ -28,6 +28,19 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
 //   RULE_DDIM_DET   eta = 0 and the reverse step: no sigma table, no noise read, no Philox rounds, no noise store
 enum { RULE_ANCESTRAL = 0, RULE_DDIM = 1, RULE_DDIM_DET = 2 };
 
+// What the network's output IS, the second COMPILE-TIME choice of the same three kernels (ModelMeanType, :305-326):
+//   MEAN_EPS  the noise: p0 = sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] eps      (_predict_xstart_from_eps, :341-346)
+//   MEAN_X0   x0-hat itself (predict_xstart=True): p0 = the output; the two tables are neither loaded nor multiplied and
+//             their pointers may be null
+// Everything behind p0 - clamp, c1 p0 + c2 x, the noise (same key, counter and stream), the stores - is shared text.  The
+// MEAN_EPS instantiations are instruction for instruction the kernels they were before MEAN existed.
+enum { MEAN_EPS = 0, MEAN_X0 = 1 };
+
+template <int MEAN>
+__device__ __forceinline__ float mean_x0hat(float r, float rm1, float xv, float out) {
+    return MEAN == MEAN_X0 ? out : r * xv - rm1 * out;
+}
+
 template <int RULE>
 __device__ __forceinline__ float rule_sigma(const float* __restrict__ t_logvar, int64_t tb) {
     if (RULE == RULE_ANCESTRAL) return tb != 0 ? expf(0.5f * t_logvar[tb]) : 0.f;
@@ -36,7 +49,7 @@ __device__ __forceinline__ float rule_sigma(const float* __restrict__ t_logvar, 
 }
 
 // x and sample may alias (the sampler updates its state in place): no __restrict__ on them.
-template <int RULE>
+template <int RULE, int MEAN>
 __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const float* __restrict__ eps,
                                                        const float* __restrict__ noise, const int64_t* __restrict__ t,
                                                        const float* __restrict__ t_recip, const float* __restrict__ t_recipm1,
@@ -46,13 +59,14 @@ __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const flo
                                                        float* __restrict__ mean_out, int inner) {
     const int b = blockIdx.y;
     const int64_t tb = t[b];
-    const float r = t_recip[tb], rm1 = t_recipm1[tb], c1 = t_c1[tb], c2 = t_c2[tb];
+    const float r = MEAN == MEAN_EPS ? t_recip[tb] : 0.f, rm1 = MEAN == MEAN_EPS ? t_recipm1[tb] : 0.f;
+    const float c1 = t_c1[tb], c2 = t_c2[tb];
     // sample = mean + [t != 0] * exp(0.5 * log_variance) * noise     (:396-400)
     const float sigma = rule_sigma<RULE>(t_logvar, tb);
     const size_t base = (size_t)b * inner;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += gridDim.x * blockDim.x) {
         const float xv = x[base + i];
-        float p0 = r * xv - rm1 * eps[base + i];   // _predict_xstart_from_eps (:341-346)
+        float p0 = mean_x0hat<MEAN>(r, rm1, xv, eps[base + i]);
         if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
         const float mean = c1 * p0 + c2 * xv;       // q_posterior_mean_variance (:228-231)
         float sv = mean;
@@ -92,7 +106,7 @@ __device__ __forceinline__ f32x4 normal4(unsigned quad, unsigned row, unsigned s
     return (f32x4){m0 * c0, m0 * s0, m1 * c1, m1 * s1};
 }
 
-template <int RULE>
+template <int RULE, int MEAN>
 __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const float* __restrict__ eps,
                                                            float* __restrict__ noise_out, const int64_t* __restrict__ t,
                                                            const float* __restrict__ t_recip, const float* __restrict__ t_recipm1,
@@ -102,7 +116,8 @@ __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const
                                                            const int64_t* __restrict__ seed) {
     const int b = blockIdx.y;
     const int64_t tb = t[b];
-    const float r = t_recip[tb], rm1 = t_recipm1[tb], c1 = t_c1[tb], c2 = t_c2[tb];
+    const float r = MEAN == MEAN_EPS ? t_recip[tb] : 0.f, rm1 = MEAN == MEAN_EPS ? t_recipm1[tb] : 0.f;
+    const float c1 = t_c1[tb], c2 = t_c2[tb];
     const float sigma = rule_sigma<RULE>(t_logvar, tb);
     const unsigned long long key = RULE != RULE_DDIM_DET ? (unsigned long long)seed[0] : 0ull;
     const unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
@@ -116,7 +131,7 @@ __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const
             const int i = 4 * qd + e;
             if (i < inner) {
                 const float xv = x[base + i];
-                float p0 = r * xv - rm1 * eps[base + i];
+                float p0 = mean_x0hat<MEAN>(r, rm1, xv, eps[base + i]);
                 if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
                 const float mean = c1 * p0 + c2 * xv;
                 sample[base + i] = RULE != RULE_DDIM_DET ? mean + sigma * z[e] : mean;
@@ -144,7 +159,7 @@ struct HeadUpdate {
     int N, T, H, W, C, clip;
 };
 
-template <int CO, int CPL, int RULE>
+template <int CO, int CPL, int RULE, int MEAN>
 __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate p) {
     extern __shared__ __attribute__((aligned(16))) float wl[];      // [CO * 9][C]
     const int tid = threadIdx.x;
@@ -208,7 +223,8 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
     const int i = ((tt * CO + co) * p.H + y) * p.W + x;             // element of the (T, C, H, W) frame stack
     const size_t at = (size_t)b * inner + i;
     const int64_t tb = p.t[b];
-    const float r = p.t_recip[tb], rm1 = p.t_recipm1[tb], c1 = p.t_c1[tb], c2 = p.t_c2[tb];
+    const float r = MEAN == MEAN_EPS ? p.t_recip[tb] : 0.f, rm1 = MEAN == MEAN_EPS ? p.t_recipm1[tb] : 0.f;
+    const float c1 = p.t_c1[tb], c2 = p.t_c2[tb];
     const float sigma = rule_sigma<RULE>(p.t_logvar, tb);
     float z = 0.f;
     if (RULE == RULE_DDIM_DET) {
@@ -220,7 +236,7 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
         z = j == 0 ? z4.x : j == 1 ? z4.y : j == 2 ? z4.z : z4.w;  // x = 4 * xq + j and W % 4 == 0: i & 3 == j
     }
     const float xv = p.x[at];
-    float p0 = r * xv - rm1 * e;
+    float p0 = mean_x0hat<MEAN>(r, rm1, xv, e);
     if (p.clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
     const float mean = c1 * p0 + c2 * xv;
     p.sample[at] = RULE != RULE_DDIM_DET ? mean + sigma * z : mean;
@@ -360,27 +376,27 @@ extern "C" int lfvdm_sampler_tick(int64_t* t, const float* model_timestep_table,
 }
 
 namespace {
-template <int RULE>
+template <int RULE, int MEAN = MEAN_EPS>
 int launch_update(const float* x, const float* eps, const float* noise, const int64_t* t, const float* recip, const float* recipm1,
                   const float* c1, const float* c2, const float* sg, int clip, float* sample, float* pred, float* mean_out, int B,
                   int inner, void* stream) {
     if (B <= 0 || inner <= 0) return LFVDM_E_SHAPE;
     int gx = (inner + 255) / 256;
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(p_sample_kernel<RULE>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise, t, recip, recipm1, c1,
+    hipLaunchKernelGGL((p_sample_kernel<RULE, MEAN>), dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise, t, recip, recipm1, c1,
                        c2, sg, clip, sample, pred, mean_out, inner);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
 
-template <int RULE>
+template <int RULE, int MEAN = MEAN_EPS>
 int launch_update_rng(const float* x, const float* eps, float* noise_out, const int64_t* t, const float* recip,
                       const float* recipm1, const float* c1, const float* c2, const float* sg, int clip, float* sample, float* pred,
                       float* mean_out, int B, int inner, const int64_t* seed, void* stream) {
     if (B <= 0 || inner <= 0 || (RULE != RULE_DDIM_DET && !seed)) return LFVDM_E_SHAPE;
     int gx = ((inner + 3) / 4 + 255) / 256;
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(p_sample_rng_kernel<RULE>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise_out, t, recip,
+    hipLaunchKernelGGL((p_sample_rng_kernel<RULE, MEAN>), dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise_out, t, recip,
                        recipm1, c1, c2, sg, clip, sample, pred, mean_out, inner, seed);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
@@ -436,7 +452,7 @@ extern "C" int lfvdm_conv_out_psample_ok(int N, int H, int W, int C, int Cout) {
 }
 
 namespace {
-template <int RULE>
+template <int RULE, int MEAN = MEAN_EPS>
 int launch_head(const HeadUpdate& p, int Cout, void* stream) {
     if (int rc = lfvdm_conv_out_psample_ok(p.N, p.H, p.W, p.C, Cout)) return rc;
     const long quads = (long)p.N * p.H * (p.W / 4);
@@ -444,7 +460,7 @@ int launch_head(const HeadUpdate& p, int Cout, void* stream) {
     const size_t lds = (size_t)Cout * 9 * p.C * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
     const int C = p.C;
-#define LFVDM_HEAD(CO, CPL) hipLaunchKernelGGL((conv_out_psample_kernel<CO, CPL, RULE>), grid, dim3(256), lds, s, p)
+#define LFVDM_HEAD(CO, CPL) hipLaunchKernelGGL((conv_out_psample_kernel<CO, CPL, RULE, MEAN>), grid, dim3(256), lds, s, p)
     if (Cout == 4) {
         if (C == 64) LFVDM_HEAD(4, 1); else if (C == 128) LFVDM_HEAD(4, 2); else LFVDM_HEAD(4, 4);
     } else {
@@ -480,6 +496,80 @@ extern "C" int lfvdm_conv_out_ddim(const float* act, const float* Wp, const floa
                           nullptr, t, sigma ? seed : nullptr, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, sigma, B * T, T, H, W, C,
                           clip};
     return sigma ? launch_head<RULE_DDIM>(p, Cout, stream) : launch_head<RULE_DDIM_DET>(p, Cout, stream);
+}
+
+// ---- the entries that carry the mean type (include/lfvdm_hip.h: LFVDM_RULE_* / LFVDM_MEAN_*).  rule DDIM with
+// sigma == NULL is the deterministic instantiation, as in lfvdm_ddim_sample.  The six entries above stay what they are.
+namespace {
+// -> RULE_* of the template grid, or -1
+int grid_rule(int rule, const float* sg) {
+    if (rule == LFVDM_RULE_ANCESTRAL) return sg ? RULE_ANCESTRAL : -1;
+    if (rule == LFVDM_RULE_DDIM) return sg ? RULE_DDIM : RULE_DDIM_DET;
+    return -1;
+}
+bool mean_ok(int mean_type, const float* recip, const float* recipm1) {
+    if (mean_type == LFVDM_MEAN_X0) return true;
+    return mean_type == LFVDM_MEAN_EPS && recip && recipm1;
+}
+}  // namespace
+
+namespace {
+template <int V> struct Const { static constexpr int value = V; };
+// f(Const<RULE>, Const<MEAN>) on the cell of the 3 x 2 template grid
+template <class F>
+int on_grid(int R, int mean_type, F f) {
+    const bool x0 = mean_type == LFVDM_MEAN_X0;
+    switch (R) {
+        case RULE_ANCESTRAL: return x0 ? f(Const<RULE_ANCESTRAL>(), Const<MEAN_X0>()) : f(Const<RULE_ANCESTRAL>(), Const<MEAN_EPS>());
+        case RULE_DDIM: return x0 ? f(Const<RULE_DDIM>(), Const<MEAN_X0>()) : f(Const<RULE_DDIM>(), Const<MEAN_EPS>());
+        case RULE_DDIM_DET: return x0 ? f(Const<RULE_DDIM_DET>(), Const<MEAN_X0>()) : f(Const<RULE_DDIM_DET>(), Const<MEAN_EPS>());
+    }
+    return LFVDM_E_SHAPE;
+}
+}  // namespace
+
+extern "C" int lfvdm_update_x0(const float* x, const float* model_out, const float* noise, const int64_t* t,
+                               const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* c1, const float* c2,
+                               const float* sg, int rule, int mean_type, int clip, float* sample, float* pred_xstart,
+                               float* mean_out, int B, int inner, void* stream) {
+    const int R = grid_rule(rule, sg);
+    if (R < 0 || !mean_ok(mean_type, sqrt_recip_acp, sqrt_recipm1_acp)) return LFVDM_E_SHAPE;
+    if (!x || !model_out || !t || !c1 || !c2 || !sample || (R != RULE_DDIM_DET && !noise)) return LFVDM_E_SHAPE;
+    return on_grid(R, mean_type, [&](auto r, auto m) {
+        return launch_update<decltype(r)::value, decltype(m)::value>(
+            x, model_out, decltype(r)::value == RULE_DDIM_DET ? nullptr : noise, t, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg,
+            clip, sample, pred_xstart, mean_out, B, inner, stream);
+    });
+}
+
+extern "C" int lfvdm_update_rng_x0(const float* x, const float* model_out, float* noise_out, const int64_t* t,
+                                   const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* c1, const float* c2,
+                                   const float* sg, int rule, int mean_type, int clip, float* sample, float* pred_xstart,
+                                   float* mean_out, int B, int inner, const int64_t* seed, void* stream) {
+    const int R = grid_rule(rule, sg);
+    if (R < 0 || !mean_ok(mean_type, sqrt_recip_acp, sqrt_recipm1_acp)) return LFVDM_E_SHAPE;
+    if (!x || !model_out || !t || !c1 || !c2 || !sample) return LFVDM_E_SHAPE;
+    return on_grid(R, mean_type, [&](auto r, auto m) {
+        constexpr bool det = decltype(r)::value == RULE_DDIM_DET;
+        return launch_update_rng<decltype(r)::value, decltype(m)::value>(
+            x, model_out, det ? nullptr : noise_out, t, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, clip, sample, pred_xstart,
+            mean_out, B, inner, det ? nullptr : seed, stream);
+    });
+}
+
+extern "C" int lfvdm_conv_out_update_x0(const float* act, const float* Wp, const float* bias, float* out, const float* x,
+                                        const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
+                                        const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg,
+                                        int rule, int mean_type, int clip, float* sample, float* pred_xstart, float* mean_out,
+                                        int B, int T, int H, int W, int C, int Cout, const int64_t* seed, void* stream) {
+    const int R = grid_rule(rule, sg);
+    if (R < 0 || !mean_ok(mean_type, sqrt_recip_acp, sqrt_recipm1_acp)) return LFVDM_E_SHAPE;
+    if (B <= 0 || T <= 0 || !act || !Wp || !bias || !x || !sample || !t || !c1 || !c2) return LFVDM_E_SHAPE;
+    const bool det = R == RULE_DDIM_DET;
+    if (!det && !noise_in && !seed) return LFVDM_E_SHAPE;
+    const HeadUpdate p = {act, Wp, bias, x, det ? nullptr : noise_in, out, det ? nullptr : noise_out, sample, pred_xstart, mean_out,
+                          t, det ? nullptr : seed, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, B * T, T, H, W, C, clip};
+    return on_grid(R, mean_type, [&](auto r, auto m) { return launch_head<decltype(r)::value, decltype(m)::value>(p, Cout, stream); });
 }
 
 extern "C" int lfvdm_masked_mse(const float* a, const float* b, const float* mask, float* out, int B, int T,

@@ -773,13 +773,14 @@ class Plan:
             self._fill_R(blk * H, min((blk + 1) * H, self.time_steps), (blk % 2) * H)
         self._loaded = {}
 
-    def fuse_head_update(self, t_buf, tables, clip, seed, noise, pred, inject_noise, ddim=None):
+    def fuse_head_update(self, t_buf, tables, clip, seed, noise, pred, inject_noise, ddim=None, predict_xstart=False):
         """Sampler only (its plan is private): replace the last launch - the output convolution - by
         lfvdm_conv_out_psample, which also does the x_{t-1} update on ``x_in`` (reference gaussian_diffusion.py:369-401)
         with the chain's in-kernel noise (or ``noise`` as given when ``inject_noise``).  -> False if the shape is not
         covered (the sampler then issues the update as its own launch).  ``ddim``: the device tables k1 / k2 / sigma of
         ``GaussianDiffusion.ddim_tables`` - the DDIM rule in the same launch (lfvdm_conv_out_ddim; sigma None: deterministic,
-        no noise buffer and no seed are handed to the kernel)."""
+        no noise buffer and no seed are handed to the kernel).  ``predict_xstart``: the network returns x0-hat - the same
+        launch in its MEAN_X0 form (lfvdm_conv_out_update_x0; no sqrt_recip tables are handed over)."""
         L = nat.lib()
         h = self.head
         if self.head_fused:
@@ -787,6 +788,20 @@ class Plan:
         if h["step"] != len(self.steps) - 1 or L.lfvdm_conv_out_psample_ok(self.B * self.T, self.H, self.W, h["C"], h["Cout"]) != 0:
             return False
         self.keep.append((t_buf, tables, seed, noise, pred, ddim))
+        if predict_xstart:
+            det = ddim is not None and ddim["sigma"] is None
+            if ddim is not None:
+                c1, c2, sg, rule = ddim["k1"], ddim["k2"], ddim["sigma"], nat.RULE_DDIM
+            else:
+                c1, c2, sg = tables["posterior_mean_coef1"], tables["posterior_mean_coef2"], tables["model_log_variance"]
+                rule = nat.RULE_ANCESTRAL
+            args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in),
+                    _p(noise) if inject_noise and not det else None, None if inject_noise or det else _p(noise), _p(t_buf),
+                    None, None, _p(c1), _p(c2), None if det else _p(sg), rule, nat.MEAN_X0, int(bool(clip)), _p(self.x_in),
+                    _p(pred), None, self.B, self.T, self.H, self.W, h["C"], h["Cout"], None if det else _p(seed))
+            self.steps[h["step"]] = (L.lfvdm_conv_out_update_x0, args)
+            self.head_fused = True
+            return True
         if ddim is not None:
             det = ddim["sigma"] is None
             args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in),

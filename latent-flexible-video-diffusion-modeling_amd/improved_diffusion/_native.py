@@ -134,6 +134,9 @@ _SIGS = {
     "lfvdm_ddim_sample": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_ddim_sample_rng": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_i, c_i, c_fp, c_fp], c_i),
     "lfvdm_conv_out_ddim": ([c_fp] * 13 + [c_i, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp], c_i),
+    "lfvdm_update_x0": ([c_fp] * 9 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i, c_i, c_fp], c_i),
+    "lfvdm_update_rng_x0": ([c_fp] * 9 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i, c_i, c_fp, c_fp], c_i),
+    "lfvdm_conv_out_update_x0": ([c_fp] * 13 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i] * 6 + [c_fp, c_fp], c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_bwd_stats": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp], c_i),
     "lfvdm_gn_bwd_apply": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
@@ -691,6 +694,40 @@ def conv_out_ddim(act, wp, bias, eps_out, x, noise_in, noise_out, t, recip, reci
                                     ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1), ptr(k2), ptr(sigma), int(bool(clip)),
                                     ptr(sample), ptr(pred), B, T, H, W, act.shape[-1], Cout,
                                     ptr(seed, torch.int64) if seed is not None else None, stream()), "lfvdm_conv_out_ddim")
+
+
+RULE_ANCESTRAL, RULE_DDIM = 0, 1      # LFVDM_RULE_* / LFVDM_MEAN_* of include/lfvdm_hip.h
+MEAN_EPS, MEAN_X0 = 0, 1
+
+
+def update_x0(x, out, noise, t, recip, recipm1, c1, c2, sg, rule, mean_type, clip, sample, pred=None, mean=None):
+    """The x_{t-1} update with given noise for either mean type (lfvdm_update_x0).  ``out``: the network's output;
+    MEAN_X0: ``recip`` / ``recipm1`` may be None; RULE_DDIM with ``sg=None``: deterministic, ``noise`` is not read."""
+    B = x.shape[0]
+    check(lib().lfvdm_update_x0(ptr(x), ptr(out), ptr(noise), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1), ptr(c2),
+                                ptr(sg), int(rule), int(mean_type), int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B,
+                                x.numel() // B, stream()), "lfvdm_update_x0")
+
+
+def update_rng_x0(x, out, noise_out, t, recip, recipm1, c1, c2, sg, rule, mean_type, clip, sample, seed, pred=None, mean=None):
+    """The same update with the noise drawn in the kernel (lfvdm_update_rng_x0; lfvdm_p_sample_rng's stream)."""
+    B = x.shape[0]
+    check(lib().lfvdm_update_rng_x0(ptr(x), ptr(out), ptr(noise_out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1),
+                                    ptr(c2), ptr(sg), int(rule), int(mean_type), int(bool(clip)), ptr(sample), ptr(pred),
+                                    ptr(mean), B, x.numel() // B, ptr(seed, torch.int64) if seed is not None else None, stream()),
+          "lfvdm_update_rng_x0")
+
+
+def conv_out_update_x0(act, wp, bias, out, x, noise_in, noise_out, t, recip, recipm1, c1, c2, sg, rule, mean_type, clip, sample,
+                       seed, pred=None, mean=None):
+    """The U-Net's output conv and the update in one launch for either mean type (lfvdm_conv_out_update_x0); layouts as
+    conv_out_psample."""
+    B, T, Cout, H, W = x.shape
+    check(lib().lfvdm_conv_out_update_x0(ptr(act), ptr(wp), ptr(bias), ptr(out), ptr(x), ptr(noise_in), ptr(noise_out),
+                                         ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1), ptr(c2), ptr(sg), int(rule),
+                                         int(mean_type), int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B, T, H, W,
+                                         act.shape[-1], Cout, ptr(seed, torch.int64) if seed is not None else None, stream()),
+          "lfvdm_conv_out_update_x0")
 
 
 def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):

@@ -9,10 +9,17 @@ What is native here
     forward + noise draw + update + t decrement): no host work inside the 1000-step loop;
   * DDIM (``ddim_sample``, ``ddim_reverse_sample``, ``ddim_sample_loop[_progressive]``, reference :524-685) is a second
     update rule of the same kernels and of the same replayed step; its per-timestep coefficients are folded on the host in
-    float64 (``ddim_coefficients``).
+    float64 (``ddim_coefficients``);
+  * x0-prediction models (``predict_xstart=True``, ``ModelMeanType.START_X``, reference :305-326, :779-788) are the second
+    mean type of the same kernels, chosen at compile time next to the rule: x0-hat is the clamped network output, the
+    ``sqrt_recip`` / ``sqrt_recipm1`` tables are not read, everything behind x0-hat (posterior mean or folded DDIM rule,
+    noise, the replayed step, the fused head launch) is shared with epsilon prediction, and ``training_losses`` regresses
+    on ``x_start``.
 
-Out of scope (not reached by the default CLIs): learned-sigma / KL losses,
-bits-per-dim loops, the VAE (needs a network fetch) — they raise NotImplementedError.
+Out of scope (not reached by the default CLIs): learned-sigma / KL losses, bits-per-dim loops,
+``ModelMeanType.PREVIOUS_X`` (no factory of the reference builds it; its x0-hat multiplies by 1 / posterior_mean_coef1[t],
+about 8e3 at t = 999 of the linear schedule, and would need folded tables and an error analysis of its own), the VAE
+(needs a network fetch) — they raise NotImplementedError.
 """
 import enum
 import math
@@ -224,17 +231,37 @@ class GaussianDiffusion:
         return t
 
     def _check_native_modes(self):
-        if self.model_mean_type != ModelMeanType.EPSILON:
-            raise NotImplementedError("only epsilon prediction (predict_xstart=False, the default) is native")
+        if self.model_mean_type == ModelMeanType.PREVIOUS_X:
+            raise NotImplementedError("ModelMeanType.PREVIOUS_X is not native: epsilon prediction (the default) and x0 "
+                                      "prediction (predict_xstart=True, START_X) are")
+        if self.model_mean_type not in (ModelMeanType.EPSILON, ModelMeanType.START_X):
+            raise NotImplementedError(f"unknown model mean type {self.model_mean_type!r}")
         if self.model_var_type not in (ModelVarType.FIXED_LARGE, ModelVarType.FIXED_SMALL):
             raise NotImplementedError("only fixed sigma (learn_sigma=False, the default) is native")
 
+    @property
+    def predicts_xstart(self):
+        """The network's output is x0-hat (predict_xstart=True), not the noise."""
+        return self.model_mean_type == ModelMeanType.START_X
+
+    def _xstart_from_output(self, x_t, t, model_output):
+        """x0-hat before ``denoised_fn`` and the clamp (reference :311-326)."""
+        if self.predicts_xstart:
+            return model_output
+        return self._predict_xstart_from_eps(x_t, t, model_output)
+
     # ------------------------------------------------------------------ p(x_{t-1} | x_t)
+    # ``eps`` below is the network's output: the noise, or x0-hat when ``predicts_xstart``
     def _p_update(self, x, eps, t, noise, clip_denoised, want_mean=False):
         tb = self.tables(x.device)
         sample = th.empty_like(x, memory_format=th.contiguous_format)
         pred = th.empty_like(sample)
         mean = th.empty_like(sample) if want_mean else None
+        if self.predicts_xstart:
+            nat.update_x0(x.contiguous(), eps.contiguous(), noise.contiguous() if noise is not None else x.contiguous(),
+                          t.to(th.int64).contiguous(), None, None, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
+                          tb["model_log_variance"], nat.RULE_ANCESTRAL, nat.MEAN_X0, clip_denoised, sample, pred, mean)
+            return sample, pred, mean
         nat.p_sample(x.contiguous(), eps.contiguous(), noise.contiguous() if noise is not None else x.contiguous(),
                      t.to(th.int64).contiguous(), tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"],
                      tb["posterior_mean_coef1"], tb["posterior_mean_coef2"], tb["model_log_variance"], clip_denoised,
@@ -246,7 +273,7 @@ class GaussianDiffusion:
         :305-309).  ``denoised_fn`` is arbitrary Python on a tensor, so this rarely used variant is composed of
         elementwise device ops around it instead of the fused kernel."""
         n = x.dim()
-        pred = denoised_fn(self._predict_xstart_from_eps(x, t, eps))
+        pred = denoised_fn(self._xstart_from_output(x, t, eps))
         if clip_denoised:
             pred = pred.clamp(-1, 1)
         mean, _, _ = self.q_posterior_mean_variance(pred, x, t)
@@ -258,7 +285,7 @@ class GaussianDiffusion:
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                         return_attn_weights=False):
-        """Model mean/variance and x0-hat at step t (reference :244-339), epsilon + fixed sigma."""
+        """Model mean/variance and x0-hat at step t (reference :244-339), epsilon or x0 prediction + fixed sigma."""
         self._check_native_modes()
         model_kwargs = model_kwargs or {}
         B = x.shape[0]
@@ -385,6 +412,11 @@ class GaussianDiffusion:
         tb, co = self.tables(x.device), self.ddim_tables(x.device, eta, reverse)
         sample = th.empty_like(x, memory_format=th.contiguous_format)
         pred = th.empty_like(sample)
+        if self.predicts_xstart:    # the folded rule is written in terms of x0-hat: the same k1 / k2 / sigma
+            nat.update_x0(x.contiguous(), eps.contiguous(), noise.contiguous() if co["sigma"] is not None else None,
+                          t.to(th.int64).contiguous(), None, None, co["k1"], co["k2"], co["sigma"], nat.RULE_DDIM, nat.MEAN_X0,
+                          clip_denoised, sample, pred)
+            return sample, pred
         nat.ddim_sample(x.contiguous(), eps.contiguous(), noise.contiguous() if co["sigma"] is not None else None,
                         t.to(th.int64).contiguous(), tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"],
                         co["k1"], co["k2"], co["sigma"], clip_denoised, sample, pred)
@@ -394,7 +426,7 @@ class GaussianDiffusion:
         """The two-launch route of ``_p_update_denoised`` for DDIM: x0-hat, the user's function, the clamp, then the folded
         rule as elementwise device ops."""
         n = x.dim()
-        pred = denoised_fn(self._predict_xstart_from_eps(x, t, eps))
+        pred = denoised_fn(self._xstart_from_output(x, t, eps))
         if clip_denoised:
             pred = pred.clamp(-1, 1)
         co = self.ddim_tables(x.device, eta, reverse)
@@ -522,8 +554,8 @@ class GaussianDiffusion:
     def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, latent_mask=None, eval_mask=None):
         """{'mse','eval-mse','loss'} per batch element (reference :722-796, MSE branch).
 
-        mse = mean over (T,C,H,W) of (eps - eps_hat)^2 * mask, NOT normalised by the mask count
-        (reference nn.py:86-92)."""
+        mse = mean over (T,C,H,W) of (target - model_output)^2 * mask, NOT normalised by the mask count
+        (reference nn.py:86-92); target = the noise, or ``x_start`` for an x0-prediction model (reference :779-785)."""
         self._check_native_modes()
         if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
             raise NotImplementedError("KL losses (use_kl=True) are outside the native hot path")
@@ -534,9 +566,12 @@ class GaussianDiffusion:
         model_output, _ = model(x_t, timesteps=self._scale_timesteps(t), **model_kwargs)
         assert model_output.shape == noise.shape == x_start.shape
         from ._autograd import masked_mse
-        terms = {"mse": masked_mse(noise, model_output, latent_mask)}
+        # (model_kwargs["x0"] is the window's conditioning frames - an INPUT of the network in either mode; the regression
+        # target of an x0-prediction model is x_start, the clean latents of all frames)
+        target = x_start if self.predicts_xstart else noise
+        terms = {"mse": masked_mse(target, model_output, latent_mask)}
         with th.no_grad():
-            terms["eval-mse"] = masked_mse(noise, model_output.detach(), eval_mask)
+            terms["eval-mse"] = masked_mse(target, model_output.detach(), eval_mask)
         terms["loss"] = terms["mse"]
         return terms
 
@@ -647,6 +682,10 @@ class GraphSampler:
         if self.rule[0] not in ("ancestral", "ddim") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
             raise ValueError(f"unknown update rule {rule!r}")
         self.ddim = None                # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic)
+        diffusion._check_native_modes()
+        # the mean type is fixed for the life of the captured graphs, as the rule is (``_samplers`` lives on the diffusion
+        # object: it needs no key element).  Not to be confused with model_kwargs["x0"], the conditioning frames
+        self.x0_mode = diffusion.predicts_xstart
         B, T, Cx, H, W = self.shape
         from ._engine import Plan
         # a private plan: the sampler's state lives in its static buffers, so it must not be shared
@@ -704,7 +743,7 @@ class GraphSampler:
         fused = (os.environ.get("LFVDM_FUSED_HEAD", "1") != "0"
                  and (det or self.inject_noise or os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
                  and pl.fuse_head_update(self.t_buf, tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
-                                         ddim=dd))
+                                         ddim=dd, predict_xstart=self.x0_mode))
         if pl.time_steps and os.environ.get("LFVDM_TICK_IN_CONV", "1") != "0":
             pl.launch(tick=(self.t_buf, self.ts_table))      # the clock rides in the first launch of the forward
             self.extra_launches = 1                           # (the update; bench.py reports launches per step)
@@ -714,6 +753,22 @@ class GraphSampler:
             self.extra_launches = 2
         if fused:
             self.extra_launches -= 1
+            return
+        if self.x0_mode:      # the three stand-alone updates of an x0-prediction model: the same launches, MEAN_X0
+            if dd is not None:
+                c1, c2, sg, rule = dd["k1"], dd["k2"], dd["sigma"], nat.RULE_DDIM
+            else:
+                c1, c2, sg = tb["posterior_mean_coef1"], tb["posterior_mean_coef2"], tb["model_log_variance"]
+                rule = nat.RULE_ANCESTRAL
+            if det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch"):
+                nat.update_rng_x0(pl.x_in, pl.out, None if det else self.noise, self.t_buf, None, None, c1, c2, sg, rule,
+                                  nat.MEAN_X0, self.clip, pl.x_in, None if det else self.seed, self.pred)
+                return
+            if not self.inject_noise:
+                self.extra_launches = getattr(self, "extra_launches", 2) + 1
+                self.noise.normal_()
+            nat.update_x0(pl.x_in, pl.out, self.noise, self.t_buf, None, None, c1, c2, sg, rule, nat.MEAN_X0, self.clip, pl.x_in,
+                          self.pred)
             return
         if dd is not None:
             recip, recipm1 = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
