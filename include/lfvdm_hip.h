@@ -615,6 +615,36 @@ int lfvdm_masked_mse(const float* a, const float* b, const float* mask, float* o
 int lfvdm_masked_mse_bwd(const float* target, const float* pred, const float* mask, const float* g, float* dpred, int B, int T,
                          int frame_inner, void* stream);
 
+/* One term of the variational bound per batch row, in bits per dimension (_vb_terms_bpd, gaussian_diffusion.py:687-720
+ * with losses.py:12-77), fixed sigma, one pass over x_start / x_t / model_out (each [B][T][frame_inner]):
+ *   x0-hat     = LFVDM_MEAN_EPS: sqrt_recip_acp[t] x_t - sqrt_recipm1_acp[t] model_out | LFVDM_MEAN_X0: model_out,
+ *                clamped to [-1, 1] if clip
+ *   mean_model = c1[t] x0-hat + c2[t] x_t, mean_true = c1[t] x_start + c2[t] x_t      (c1 / c2 = posterior_mean_coef1 / 2)
+ *   t[b] != 0:   normal_kl(mean_true, post_log_var[t]; mean_model, model_log_var[t])
+ *   t[b] == 0:   -discretized_gaussian_log_likelihood(x_start; mean_model, 0.5 model_log_var[t]) - the reference's tanh CDF,
+ *                its clamp(min=1e-12) of cdf_plus, 1 - cdf_min and cdf_delta, its x < -0.999 / x > 0.999 branches
+ *   vb[b]      = mean over the T * frame_inner elements of term * mask[b][frame] / ln 2   (NOT divided by the mask count)
+ * post_log_var = posterior_log_variance_clipped, model_log_var = the fixed-sigma table (large or small); mask [B][T] or NULL.
+ * Optional results of the same pass (NULL: not computed): xstart_mse[b] = mean((x0-hat - x_start)^2 mask), eps_mse[b] =
+ * mean((eps - noise)^2 mask) with eps recovered from x0-hat as _predict_eps_from_xstart does (needs noise and, in either
+ * mode, the two sqrt_recip tables - LFVDM_MEAN_X0 without eps_mse never reads them and they may be NULL), pred_xstart = the
+ * dense x0-hat.  The three per-row results are written at [b * out_ld + col], col = col_base - t[b] for col_base >= 0 (the
+ * bits-per-dim loops: column of the descending walk, derived from the device-side clock; a column outside [0, out_ld) is
+ * not written) and col = 0 for col_base < 0 (then out_ld must be 1).  Deterministic: fixed summation order, no atomics. */
+int lfvdm_vb_terms(const float* x_start, const float* x_t, const float* model_out, const float* noise, const int64_t* t,
+                   const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* c1, const float* c2,
+                   const float* post_log_var, const float* model_log_var, const float* mask, int mean_type, int clip, float* vb,
+                   float* xstart_mse, float* eps_mse, float* pred_xstart, int B, int T, int frame_inner, int out_ld,
+                   int col_base, void* stream);
+/* d_out = g[b] * d vb[b] / d model_out in closed form, for clip = 0 only (clip != 0: LFVDM_E_UNSUPPORTED - the training
+ * loss never clips).  KL rows: -(mean_true - mean_model) exp(-model_log_var[t]) dmean/dout; decoder rows: the derivative
+ * of the tanh form, 0 where a 1e-12 clamp is active; dmean/dout = -c1 sqrt_recipm1_acp (LFVDM_MEAN_EPS) or c1
+ * (LFVDM_MEAN_X0, the two tables may be NULL); all times mask[b][frame] / (T * frame_inner * ln 2). */
+int lfvdm_vb_terms_bwd(const float* x_start, const float* x_t, const float* model_out, const int64_t* t,
+                       const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* c1, const float* c2,
+                       const float* model_log_var, const float* mask, const float* g, int mean_type, int clip, float* d_out,
+                       int B, int T, int frame_inner, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Fused AdamW + EMA + gradient-norm over one flat fp32 arena (train_util.py:346-357, nn.py:55-65).
  * torch.optim.AdamW semantics (decoupled weight decay, bias correction); ema <- rate*ema + (1-rate)*p.

@@ -34,6 +34,38 @@ def masked_mse(target, pred, mask):
     return _MaskedMSE.apply(target, pred, mask)
 
 
+class _VbTerm(th.autograd.Function):
+    """vb[b] of ``GaussianDiffusion._vb_terms_bpd`` with clip_denoised=False (reference gaussian_diffusion.py:687-720, the
+    KL training loss): one HIP launch forward (lfvdm_vb_terms), one backward (lfvdm_vb_terms_bwd, the closed-form gradient);
+    the gradient goes to the network output only.  ``tabs``: the device tables (recip, recipm1, c1, c2, post_logvar,
+    model_logvar), ``mean_type``: _native.MEAN_EPS / MEAN_X0."""
+
+    @staticmethod
+    def forward(ctx, x_start, x_t, out, t, mask, tabs, mean_type):
+        B, T = out.shape[0], out.shape[1]
+        x_start, x_t, out = x_start.contiguous(), x_t.contiguous(), out.contiguous()
+        t = t.to(th.int64).contiguous()
+        m = None if mask is None else mask.reshape(B, T).to(th.float32).contiguous()
+        recip, recipm1, c1, c2, post_lv, model_lv = tabs
+        vb = th.empty(B, device=out.device, dtype=th.float32)
+        nat.vb_terms(x_start, x_t, out, None, t, recip, recipm1, c1, c2, post_lv, model_lv, m, mean_type, False, vb)
+        ctx.save_for_backward(x_start, x_t, out, t, m)
+        ctx.tabs, ctx.mean_type = tabs, mean_type
+        return vb
+
+    @staticmethod
+    def backward(ctx, g):
+        x_start, x_t, out, t, m = ctx.saved_tensors
+        recip, recipm1, c1, c2, _, model_lv = ctx.tabs
+        d = th.empty_like(out)
+        nat.vb_terms_bwd(x_start, x_t, out, t, recip, recipm1, c1, c2, model_lv, m, g.contiguous().float(), ctx.mean_type, False, d)
+        return None, None, d, None, None, None, None
+
+
+def vb_term(x_start, x_t, out, t, mask, tabs, mean_type):
+    return _VbTerm.apply(x_start, x_t, out, t, mask, tabs, mean_type)
+
+
 def unet_apply(engine, x, x0, timesteps, frame_indices, obs_mask, latent_mask, return_attn_weights):
     from ._backward import UNetFunction
     return UNetFunction.run(engine, x, x0, timesteps, frame_indices, obs_mask, latent_mask, return_attn_weights)

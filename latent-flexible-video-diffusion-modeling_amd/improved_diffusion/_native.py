@@ -138,6 +138,8 @@ _SIGS = {
     "lfvdm_update_rng_x0": ([c_fp] * 9 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i, c_i, c_fp, c_fp], c_i),
     "lfvdm_conv_out_update_x0": ([c_fp] * 13 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i] * 6 + [c_fp, c_fp], c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
+    "lfvdm_vb_terms": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 4 + [c_i] * 5 + [c_fp], c_i),
+    "lfvdm_vb_terms_bwd": ([c_fp] * 11 + [c_i, c_i, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_bwd_stats": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp], c_i),
     "lfvdm_gn_bwd_apply": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_bwd_apply_params": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i,
@@ -728,6 +730,27 @@ def conv_out_update_x0(act, wp, bias, out, x, noise_in, noise_out, t, recip, rec
                                          int(mean_type), int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B, T, H, W,
                                          act.shape[-1], Cout, ptr(seed, torch.int64) if seed is not None else None, stream()),
           "lfvdm_conv_out_update_x0")
+
+
+def vb_terms(x_start, x_t, out, noise, t, recip, recipm1, c1, c2, post_logvar, model_logvar, mask, mean_type, clip, vb,
+             xstart_mse=None, eps_mse=None, pred=None, col_base=-1):
+    """One variational-bound term per batch row in bits per dimension (lfvdm_vb_terms).  ``out``: the network's output;
+    ``vb`` (and the optional ``xstart_mse`` / ``eps_mse``) are (B,) or (B, n) tensors - with ``col_base`` >= 0 row b is
+    written at column ``col_base - t[b]``; MEAN_X0 without ``eps_mse``: ``recip`` / ``recipm1`` may be None."""
+    B, T = x_t.shape[0], x_t.shape[1]
+    ld = vb.shape[1] if vb.dim() == 2 else 1
+    check(lib().lfvdm_vb_terms(ptr(x_start), ptr(x_t), ptr(out), ptr(noise), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1),
+                               ptr(c2), ptr(post_logvar), ptr(model_logvar), ptr(mask), int(mean_type), int(bool(clip)), ptr(vb),
+                               ptr(xstart_mse), ptr(eps_mse), ptr(pred), B, T, x_t.numel() // (B * T), ld, int(col_base),
+                               stream()), "lfvdm_vb_terms")
+
+
+def vb_terms_bwd(x_start, x_t, out, t, recip, recipm1, c1, c2, model_logvar, mask, g, mean_type, clip, d_out):
+    """d_out = g[b] * d vb[b] / d out, clip_denoised=False only (lfvdm_vb_terms_bwd)."""
+    B, T = x_t.shape[0], x_t.shape[1]
+    check(lib().lfvdm_vb_terms_bwd(ptr(x_start), ptr(x_t), ptr(out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1), ptr(c2),
+                                   ptr(model_logvar), ptr(mask), ptr(g), int(mean_type), int(bool(clip)), ptr(d_out), B, T,
+                                   x_t.numel() // (B * T), stream()), "lfvdm_vb_terms_bwd")
 
 
 def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):

@@ -16,10 +16,17 @@ What is native here
     noise, the replayed step, the fused head launch) is shared with epsilon prediction, and ``training_losses`` regresses
     on ``x_start``.
 
-Out of scope (not reached by the default CLIs): learned-sigma / KL losses, bits-per-dim loops,
+  * the variational bound (``use_kl=True`` training, ``_vb_terms_bpd``, ``_prior_bpd``, ``calc_bpd_loop[_subsampled]``,
+    reference :687-720, :743-753, :798-888, losses.py) with fixed sigma: the KL / discretized-decoder term of a batch row,
+    its x0 and epsilon MSEs and its closed-form gradient are two HIP kernels (csrc/vb_terms.hip, ``_autograd._VbTerm``);
+    ``calc_bpd_loop`` replays ONE captured hipGraph per evaluation step (clock, noise draw, q_sample, U-Net forward, term)
+    over a private plan (``BpdEvaluator``), like the samplers.
+
+Out of scope (not reached by the default CLIs): learned sigma (``learn_sigma=True``, also together with
+``use_kl``: the reference's own 5-D code path asserts on it, so there is no behaviour to match),
 ``ModelMeanType.PREVIOUS_X`` (no factory of the reference builds it; its x0-hat multiplies by 1 / posterior_mean_coef1[t],
 about 8e3 at t = 999 of the linear schedule, and would need folded tables and an error analysis of its own), the VAE
-(needs a network fetch) — they raise NotImplementedError.
+(needs a network fetch) - they raise NotImplementedError.
 """
 import enum
 import math
@@ -115,6 +122,7 @@ class GaussianDiffusion:
         self._dev_cache = {}
         self._ddim_cache = {}
         self._samplers = {}
+        self._bpd_evals = {}
         self.setup_enc_dec()
 
     # ------------------------------------------------------------------ tables on device
@@ -237,7 +245,8 @@ class GaussianDiffusion:
         if self.model_mean_type not in (ModelMeanType.EPSILON, ModelMeanType.START_X):
             raise NotImplementedError(f"unknown model mean type {self.model_mean_type!r}")
         if self.model_var_type not in (ModelVarType.FIXED_LARGE, ModelVarType.FIXED_SMALL):
-            raise NotImplementedError("only fixed sigma (learn_sigma=False, the default) is native")
+            raise NotImplementedError("only fixed sigma (learn_sigma=False, the default) is native - for the MSE and for the KL "
+                                      "(use_kl=True) losses alike")
 
     @property
     def predicts_xstart(self):
@@ -555,14 +564,23 @@ class GaussianDiffusion:
         """{'mse','eval-mse','loss'} per batch element (reference :722-796, MSE branch).
 
         mse = mean over (T,C,H,W) of (target - model_output)^2 * mask, NOT normalised by the mask count
-        (reference nn.py:86-92); target = the noise, or ``x_start`` for an x0-prediction model (reference :779-785)."""
+        (reference nn.py:86-92); target = the noise, or ``x_start`` for an x0-prediction model (reference :779-785).
+
+        KL losses (``use_kl=True``: LossType.RESCALED_KL, or LossType.KL; reference :743-753): {'loss'} alone, the
+        variational-bound term of ``t`` with clip_denoised=False over ALL frames (the masks are not used), times
+        num_timesteps for RESCALED_KL; the gradient reaches the network through ``_autograd._VbTerm``."""
         self._check_native_modes()
-        if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
-            raise NotImplementedError("KL losses (use_kl=True) are outside the native hot path")
+        if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE, LossType.KL, LossType.RESCALED_KL):
+            raise NotImplementedError(self.loss_type)
         model_kwargs = model_kwargs or {}
         if noise is None:
             noise = th.randn_like(x_start)
         x_t = self.q_sample(x_start, t, noise=noise)
+        if self.loss_type.is_vb():
+            loss = self._vb_terms(model, x_start, x_t, t, False, model_kwargs, None)["output"]
+            if self.loss_type == LossType.RESCALED_KL:
+                loss = loss * self.num_timesteps
+            return {"loss": loss}
         model_output, _ = model(x_t, timesteps=self._scale_timesteps(t), **model_kwargs)
         assert model_output.shape == noise.shape == x_start.shape
         from ._autograd import masked_mse
@@ -574,6 +592,118 @@ class GaussianDiffusion:
             terms["eval-mse"] = masked_mse(target, model_output.detach(), eval_mask)
         terms["loss"] = terms["mse"]
         return terms
+
+    # ------------------------------------------------------------------ variational bound (reference :687-720, :798-888)
+    def _wrap_model(self, model):
+        return model      # SpacedDiffusion: the timestep remap
+
+    def _vb_tables(self, device):
+        tb = self.tables(device)
+        return (tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"], tb["posterior_mean_coef1"],
+                tb["posterior_mean_coef2"], tb["posterior_log_variance_clipped"], tb["model_log_variance"])
+
+    def _vb_launch(self, x_start, x_t, out, t, clip_denoised, latent_mask, noise=None, want_pred=False):
+        """The fused launch without autograd -> vb (B,), xstart_mse / eps_mse (B,) when ``noise`` is given, pred_xstart."""
+        B, T = x_t.shape[0], x_t.shape[1]
+        dev = x_t.device
+        m = None if latent_mask is None else latent_mask.reshape(B, T).to(th.float32).contiguous()
+        vb = th.empty(B, device=dev)
+        xm = th.empty(B, device=dev) if noise is not None else None
+        em = th.empty(B, device=dev) if noise is not None else None
+        pred = th.empty_like(x_t, memory_format=th.contiguous_format) if want_pred else None
+        recip, recipm1, c1, c2, post_lv, model_lv = self._vb_tables(dev)
+        nat.vb_terms(x_start.contiguous(), x_t.contiguous(), out.contiguous(), noise.contiguous() if noise is not None else None,
+                     t.to(th.int64).contiguous(), recip, recipm1, c1, c2, post_lv, model_lv, m,
+                     nat.MEAN_X0 if self.predicts_xstart else nat.MEAN_EPS, clip_denoised, vb, xm, em, pred)
+        return vb, xm, em, pred
+
+    def _vb_terms(self, model, x_start, x_t, t, clip_denoised, model_kwargs, latent_mask, noise=None, want_pred=False):
+        self._check_native_modes()
+        model_kwargs = model_kwargs or {}
+        assert t.shape == (x_t.shape[0],) and x_start.shape == x_t.shape
+        out, _ = self._wrap_model(model)(x_t, timesteps=self._scale_timesteps(t), **model_kwargs)
+        assert out.shape == x_t.shape
+        if th.is_grad_enabled() and out.requires_grad:
+            if clip_denoised:
+                raise NotImplementedError("the gradient of a variational-bound term is native for clip_denoised=False (what the "
+                                          "KL training loss uses) only: call under th.no_grad(), or pass clip_denoised=False")
+            from ._autograd import vb_term
+            vb = vb_term(x_start, x_t, out, t, latent_mask, self._vb_tables(x_t.device),
+                         nat.MEAN_X0 if self.predicts_xstart else nat.MEAN_EPS)
+            res = {"output": vb}
+            if want_pred:
+                with th.no_grad():
+                    res["pred_xstart"] = self._xstart_from_output(x_t, t, out.detach())
+            return res
+        vb, xm, em, pred = self._vb_launch(x_start, x_t, out.detach(), t, clip_denoised, latent_mask, noise, want_pred)
+        return {"output": vb, "pred_xstart": pred, "xstart_mse": xm, "mse": em}
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None, latent_mask=None):
+        """One term of the variational bound in bits per dimension (reference :687-720) -> {'output' (N,), 'pred_xstart'}:
+        the decoder NLL at t == 0, KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t)) elsewhere.  One model call and one fused
+        launch (lfvdm_vb_terms); differentiable with respect to the model output for clip_denoised=False."""
+        res = self._vb_terms(model, x_start, x_t, t, clip_denoised, model_kwargs, latent_mask, want_pred=True)
+        return {"output": res["output"], "pred_xstart": res["pred_xstart"]}
+
+    def _prior_bpd(self, x_start, latent_mask=None):
+        """KL(q(x_T | x_0) || N(0, I)) in bits per dimension (reference :798-814); once per loop, plain device ops."""
+        from .losses import normal_kl
+        t = th.full((x_start.shape[0],), self.num_timesteps - 1, device=x_start.device, dtype=th.long)
+        qt_mean, _, qt_log_variance = self.q_mean_variance(x_start, t)
+        kl_prior = normal_kl(mean1=qt_mean, logvar1=qt_log_variance, mean2=0.0, logvar2=0.0)
+        return mean_flat(kl_prior, mask=latent_mask) / np.log(2.0)
+
+    def calc_bpd_loop_subsampled(self, model, x_start, clip_denoised=True, model_kwargs=None, latent_mask=None, t_seq=None):
+        """The variational bound over ``t_seq`` (default: every timestep, descending) in bits per dimension (reference
+        :817-882) -> {'total_bpd' (N,), 'prior_bpd' (N,), 'vb', 'xstart_mse', 'mse' (N, len(t_seq))}.  ``t_seq``: a sequence
+        of timesteps, or a 2-D numpy array with one ROW of timesteps per batch element.
+
+        The full descending walk of a native U-Net on the device with ``model_kwargs`` given replays one captured hipGraph
+        per step (``BpdEvaluator``); everything else runs one model call and one fused launch per step."""
+        from .unet import UNetVideoModel
+        B = x_start.shape[0]
+        full = list(range(self.num_timesteps))[::-1]
+        if t_seq is None:
+            t_seq = full
+        two_d = isinstance(t_seq, np.ndarray) and t_seq.ndim == 2
+        inner = getattr(model, "model", model)  # _WrappedModel -> module
+        inner = getattr(inner, "module", inner)  # DDP -> module
+        fast = (isinstance(inner, UNetVideoModel) and x_start.is_cuda and model_kwargs is not None and not two_d
+                and [int(v) for v in t_seq] == full)
+        if fast:
+            ev = self._bpd_evaluator(inner, tuple(x_start.shape), clip_denoised)
+            vb, xstart_mse, mse = ev.evaluate(x_start, model_kwargs, latent_mask)
+        else:
+            cols = t_seq.transpose() if two_d else t_seq
+            vb, xstart_mse, mse = [], [], []
+            for tv in cols:
+                if two_d:
+                    t_batch = th.as_tensor(np.ascontiguousarray(tv), device=x_start.device).long()
+                else:
+                    t_batch = th.full((B,), int(tv), device=x_start.device, dtype=th.long)
+                noise = th.randn_like(x_start)
+                x_t = self.q_sample(x_start, t_batch, noise=noise)
+                with th.no_grad():
+                    out = self._vb_terms(model, x_start, x_t, t_batch, clip_denoised, model_kwargs, latent_mask, noise=noise)
+                vb.append(out["output"])
+                xstart_mse.append(out["xstart_mse"])
+                mse.append(out["mse"])
+            vb, xstart_mse, mse = (th.stack(v, dim=1) for v in (vb, xstart_mse, mse))
+        prior_bpd = self._prior_bpd(x_start, latent_mask=latent_mask)
+        return {"total_bpd": vb.sum(dim=1) + prior_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, latent_mask=None):
+        """``calc_bpd_loop_subsampled`` over every timestep (reference :884-888)."""
+        return self.calc_bpd_loop_subsampled(model=model, x_start=x_start, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
+                                             latent_mask=latent_mask, t_seq=list(range(self.num_timesteps))[::-1])
+
+    def _bpd_evaluator(self, unet, shape, clip_denoised):
+        key = (id(unet), shape, bool(clip_denoised))
+        ev = self._bpd_evals.get(key)
+        if ev is None or ev.unet is not unet or ev.engine is not unet.native_engine():
+            self._bpd_evals.clear()       # graphs pin device memory: one evaluation shape at a time
+            ev = self._bpd_evals[key] = BpdEvaluator(self, unet, shape, clip_denoised)
+        return ev
 
     # ------------------------------------------------------------------ encode / decode boundary
     def setup_enc_dec(self):
@@ -794,6 +924,53 @@ class GraphSampler:
                      tb["sqrt_recipm1_alphas_cumprod"], tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
                      tb["model_log_variance"], self.clip, pl.x_in, self.pred, None)
 
+    def _build_chain_tables(self, frame_indices):
+        """Once per chain, plan with timestep tables: the FiLM rows (once per set of weights), this window's R tables, the
+        block the chain starts in; then the clock is put on the first timestep, so that the tuning / warm-up launches
+        find valid FiLM rows.  Shared by every replayed-step class over a private plan."""
+        pl, n = self.plan, self.diffusion.num_timesteps
+        if not pl.time_steps:
+            return
+        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
+        e0.record()
+        if pl.tables_sig != (pl.time_signature(), self._ts_key):
+            pl.build_time_tables(self.ts_table)          # once per set of weights
+        pl.build_R_tables(frame_indices)                 # once per chain: R depends on this window's frames
+        pl.ensure_R(n - 1)                               # (rolling window: the block the chain starts in)
+        e1.record()
+        self._table_events = (e0, e1)        # read lazily (table_build_ms): no host stall between windows / chains
+        self.t_buf.fill_(n)
+        pl.tick(self.t_buf, self.ts_table)
+
+    def _capture_step(self):
+        """Tune the plan (once), warm ``_step_body`` up on a side stream and capture it as ``self.graph``.  The plan's
+        input is saved and restored around it, and so is the caller's RNG stream: building the graph draws warm-up noise,
+        and a seed must give the same result whether or not this shape was seen before."""
+        import os
+        pl = self.plan
+        rng_state = th.cuda.get_rng_state(pl.dev)
+        if os.environ.get("LFVDM_AUTOTUNE", "1") != "0" and not getattr(pl, "tuned", False):
+            saved0 = pl.x_in.clone()
+            pl.launch()               # realistic operand contents for the timing runs
+            pl.autotune()
+            pl.x_in.copy_(saved0)
+        # warm-up on a side stream (sets kernel attributes, fills caches), then capture
+        saved = pl.x_in.clone()
+        self.t_buf.fill_(self.diffusion.num_timesteps)
+        s = th.cuda.Stream()
+        s.wait_stream(th.cuda.current_stream())
+        with th.cuda.stream(s):
+            self._step_body()
+        th.cuda.current_stream().wait_stream(s)
+        g = th.cuda.CUDAGraph()
+        # thread-local capture: a process group's watchdog thread may query events while this thread captures
+        with th.cuda.graph(g, capture_error_mode="thread_local"):
+            self._step_body()
+        self.graph = g
+        pl.x_in.copy_(saved)
+        th.cuda.synchronize()
+        th.cuda.set_rng_state(rng_state, pl.dev)
+
     def begin(self, img, model_kwargs):
         pl = self.plan
         B, T = pl.B, pl.T
@@ -806,43 +983,9 @@ class GraphSampler:
         with th.no_grad():
             pl.set_inputs(img, model_kwargs["x0"], th.zeros(B, device=pl.dev), model_kwargs["frame_indices"],
                           model_kwargs["obs_mask"], model_kwargs["latent_mask"])
-            if pl.time_steps:
-                e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-                e0.record()
-                if pl.tables_sig != (pl.time_signature(), self._ts_key):
-                    pl.build_time_tables(self.ts_table)          # once per set of weights
-                pl.build_R_tables(model_kwargs["frame_indices"])  # once per chain: R depends on this window's frames
-                pl.ensure_R(self.diffusion.num_timesteps - 1)    # (rolling window: the block the chain starts in)
-                e1.record()
-                self._table_events = (e0, e1)        # read lazily (table_build_ms): no host stall between windows / chains
-                self.t_buf.fill_(self.diffusion.num_timesteps)
-                pl.tick(self.t_buf, self.ts_table)               # valid FiLM rows for the tuning / warm-up launches
+            self._build_chain_tables(model_kwargs["frame_indices"])
             if self.graph is None:
-                import os
-                # building the graph draws warm-up noise: keep the caller's RNG stream untouched, so that a
-                # seed gives the same video whether or not this window shape was seen before
-                rng_state = th.cuda.get_rng_state(pl.dev)
-                if os.environ.get("LFVDM_AUTOTUNE", "1") != "0" and not getattr(pl, "tuned", False):
-                    saved0 = pl.x_in.clone()
-                    pl.launch()               # realistic operand contents for the timing runs
-                    pl.autotune()
-                    pl.x_in.copy_(saved0)
-                # warm-up on a side stream (sets kernel attributes, fills caches), then capture
-                saved = pl.x_in.clone()
-                self.t_buf.fill_(self.diffusion.num_timesteps)
-                s = th.cuda.Stream()
-                s.wait_stream(th.cuda.current_stream())
-                with th.cuda.stream(s):
-                    self._step_body()
-                th.cuda.current_stream().wait_stream(s)
-                g = th.cuda.CUDAGraph()
-                # thread-local capture: a process group's watchdog thread may query events while this thread captures
-                with th.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._step_body()
-                self.graph = g
-                pl.x_in.copy_(saved)
-                th.cuda.synchronize()
-                th.cuda.set_rng_state(rng_state, pl.dev)
+                self._capture_step()
             self.t_buf.fill_(self.diffusion.num_timesteps)     # the step pre-decrements
             self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
         self.expected_t = self.diffusion.num_timesteps - 1
@@ -917,6 +1060,102 @@ class GraphSampler:
         self._abort_unchecked = True
         self.expected_t = max(int(i) - int(n), 0)
         return {"sample": self.plan.x_in, "pred_xstart": self.pred, "attn": None}
+
+
+class BpdEvaluator(GraphSampler):
+    """One evaluation step of ``calc_bpd_loop`` (clock tick -> noise draw -> q_sample into the plan's input -> U-Net forward
+    -> lfvdm_vb_terms into column j of the (N, T) results) captured as a hipGraph over a private plan with timestep
+    tables; ``step`` is a single replay.  The table build, the warm-up and capture, the chain-timeout check and the
+    fall-back are ``GraphSampler``'s; the step body, its buffers and ``begin`` are its own.  The column index is derived on
+    the device from the clock (num_timesteps - 1 - t)."""
+
+    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False):
+        # inject_noise (parity tests): the replayed step READS ``self.noise`` - the caller fills it before every ``step``
+        self.diffusion, self.unet, self.shape = diffusion, unet, tuple(shape)
+        self.clip = bool(clip_denoised)
+        self.inject_noise = bool(inject_noise)
+        diffusion._check_native_modes()
+        self.x0_mode = diffusion.predicts_xstart
+        B, T, Cx, H, W = self.shape
+        from ._engine import Plan
+        self.engine = unet.native_engine()
+        self.plan = Plan(self.engine, B, T, H, W, False, time_steps=diffusion.num_timesteps)
+        self.plan.refresh_weights()
+        dev = self.plan.dev
+        self.tb = diffusion.tables(dev)
+        self.ts_table = diffusion.model_timestep_table(dev)
+        self._ts_key = tuple(self.ts_table.tolist())
+        self._table_events = None
+        # the evaluator always walks with timestep tables (GraphSampler also serves plans without them); what the inherited
+        # _build_chain_tables / _capture_step / chain_timed_out / fall_back read is set below, nothing else of the sampler
+        assert self.plan.time_steps == diffusion.num_timesteps and self.plan.t_sel is not None
+        self.t_buf = self.plan.t_sel
+        n = diffusion.num_timesteps
+        self.x_start = th.empty(self.shape, device=dev)
+        self.noise = th.empty(self.shape, device=dev)
+        self.mask = th.ones(B, T, device=dev)
+        self.vb, self.xstart_mse, self.mse = (th.zeros(B, n, device=dev) for _ in range(3))
+        self.graph = self.graph_k = None
+        self.expected_t = None
+        self._abort_unchecked = False
+        self.chain_timeouts = 0
+
+    def _step_body(self):
+        pl, tb, d = self.plan, self.tb, self.diffusion
+        pl.tick(self.t_buf, self.ts_table)          # t <- max(t - 1, 0), model timestep and FiLM rows of the new t
+        if not self.inject_noise:
+            self.noise.normal_()                    # torch's graph-safe generator (th.manual_seed fixes the evaluation)
+        nat.q_sample(self.x_start, self.noise, self.t_buf, tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"], pl.x_in)
+        pl.launch()
+        recip, recipm1, c1, c2, post_lv, model_lv = d._vb_tables(pl.dev)
+        nat.vb_terms(self.x_start, pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, c1, c2, post_lv, model_lv, self.mask,
+                     nat.MEAN_X0 if self.x0_mode else nat.MEAN_EPS, self.clip, self.vb, self.xstart_mse, self.mse, None,
+                     col_base=d.num_timesteps - 1)
+
+    def begin(self, x_start, model_kwargs, latent_mask=None):
+        pl = self.plan
+        B, T = pl.B, pl.T
+        if pl._sig != pl.weight_signature():
+            pl.refresh_weights()
+        with th.no_grad():
+            self.x_start.copy_(x_start)
+            if latent_mask is None:
+                self.mask.fill_(1.0)
+            else:
+                self.mask.copy_(latent_mask.reshape(B, T))
+            pl.set_inputs(self.x_start, model_kwargs["x0"], th.zeros(B, device=pl.dev), model_kwargs["frame_indices"],
+                          model_kwargs["obs_mask"], model_kwargs["latent_mask"])
+            self._build_chain_tables(model_kwargs["frame_indices"])
+            if self.graph is None:
+                self._capture_step()
+            self.t_buf.fill_(self.diffusion.num_timesteps)      # the step pre-decrements
+        self.expected_t = self.diffusion.num_timesteps - 1
+
+    def step(self, i):
+        """The term of timestep ``i`` -> column num_timesteps - 1 - i of ``vb`` / ``xstart_mse`` / ``mse``."""
+        if i != self.expected_t:
+            self.t_buf.fill_(i + 1)
+        self.plan.ensure_R(i)
+        self.graph.replay()
+        self._abort_unchecked = True
+        self.expected_t = max(i - 1, 0)
+
+    def run(self, i, n):
+        raise NotImplementedError("the evaluator walks one step per replay: use step() / evaluate()")
+
+    def evaluate(self, x_start, model_kwargs, latent_mask=None):
+        """Every timestep, descending -> fresh (N, T) copies of vb, xstart_mse, mse.  A persistent level chain that gave
+        up a wait leaves garbage behind: the walk is then run again, one launch per stage (the samplers' protocol)."""
+        n = self.diffusion.num_timesteps
+        for attempt in range(2):
+            self.begin(x_start, model_kwargs, latent_mask)
+            for i in range(n - 1, -1, -1):
+                self.step(i)
+            if attempt == 0 and self.chain_timed_out():
+                self.fall_back()
+                continue
+            break
+        return self.vb.clone(), self.xstart_mse.clone(), self.mse.clone()
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):
