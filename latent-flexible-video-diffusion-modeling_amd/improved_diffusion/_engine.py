@@ -30,6 +30,22 @@ def _p(t):
     return t.data_ptr()
 
 
+def update_args(tables, ddim=None, predict_xstart=False):
+    """(recip, recipm1, c1, c2, sg, RULE_*, MEAN_*): what the three general update entries (lfvdm_update_x0,
+    lfvdm_update_rng_x0, lfvdm_conv_out_update_x0) take, from the device tables of ``GaussianDiffusion.tables`` and, for
+    the DDIM rule, of ``GaussianDiffusion.ddim_tables``.  Ancestral: the posterior coefficients and the model's log
+    variance; DDIM: the folded k1 / k2 / sigma (sigma None: the deterministic instantiation).  An x0-prediction model
+    hands no sqrt_recip tables over.  The only place that knows this mapping."""
+    if ddim is not None:
+        c1, c2, sg, rule = ddim["k1"], ddim["k2"], ddim["sigma"], nat.RULE_DDIM
+    else:
+        c1, c2, sg = tables["posterior_mean_coef1"], tables["posterior_mean_coef2"], tables["model_log_variance"]
+        rule = nat.RULE_ANCESTRAL
+    if predict_xstart:
+        return None, None, c1, c2, sg, rule, nat.MEAN_X0
+    return tables["sqrt_recip_alphas_cumprod"], tables["sqrt_recipm1_alphas_cumprod"], c1, c2, sg, rule, nat.MEAN_EPS
+
+
 # LFVDM_SPATIAL_FUSED=0: keep the qkv projection of the spatial attention as its own GEMM launch (A/B aid)
 SPATIAL_FUSED = os.environ.get("LFVDM_SPATIAL_FUSED", "1") != "0"
 # LFVDM_PROJ_GN=0: keep the temporal output projection and the spatial GroupNorm of the 16x16 level as two launches (A/B aid)
@@ -775,12 +791,13 @@ class Plan:
 
     def fuse_head_update(self, t_buf, tables, clip, seed, noise, pred, inject_noise, ddim=None, predict_xstart=False):
         """Sampler only (its plan is private): replace the last launch - the output convolution - by
-        lfvdm_conv_out_psample, which also does the x_{t-1} update on ``x_in`` (reference gaussian_diffusion.py:369-401)
+        lfvdm_conv_out_update_x0, which also does the x_{t-1} update on ``x_in`` (reference gaussian_diffusion.py:369-401)
         with the chain's in-kernel noise (or ``noise`` as given when ``inject_noise``).  -> False if the shape is not
         covered (the sampler then issues the update as its own launch).  ``ddim``: the device tables k1 / k2 / sigma of
-        ``GaussianDiffusion.ddim_tables`` - the DDIM rule in the same launch (lfvdm_conv_out_ddim; sigma None: deterministic,
-        no noise buffer and no seed are handed to the kernel).  ``predict_xstart``: the network returns x0-hat - the same
-        launch in its MEAN_X0 form (lfvdm_conv_out_update_x0; no sqrt_recip tables are handed over)."""
+        ``GaussianDiffusion.ddim_tables`` - the DDIM rule (sigma None: deterministic, no noise buffer and no seed are handed
+        to the kernel).  ``predict_xstart``: the network returns x0-hat (no sqrt_recip tables are handed over).  Every rule
+        and mean type goes through this one general entry (``update_args``); lfvdm_conv_out_psample and
+        lfvdm_conv_out_ddim launch the same kernels and remain exported for users of the C ABI."""
         L = nat.lib()
         h = self.head
         if self.head_fused:
@@ -788,36 +805,14 @@ class Plan:
         if h["step"] != len(self.steps) - 1 or L.lfvdm_conv_out_psample_ok(self.B * self.T, self.H, self.W, h["C"], h["Cout"]) != 0:
             return False
         self.keep.append((t_buf, tables, seed, noise, pred, ddim))
-        if predict_xstart:
-            det = ddim is not None and ddim["sigma"] is None
-            if ddim is not None:
-                c1, c2, sg, rule = ddim["k1"], ddim["k2"], ddim["sigma"], nat.RULE_DDIM
-            else:
-                c1, c2, sg = tables["posterior_mean_coef1"], tables["posterior_mean_coef2"], tables["model_log_variance"]
-                rule = nat.RULE_ANCESTRAL
-            args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in),
-                    _p(noise) if inject_noise and not det else None, None if inject_noise or det else _p(noise), _p(t_buf),
-                    None, None, _p(c1), _p(c2), None if det else _p(sg), rule, nat.MEAN_X0, int(bool(clip)), _p(self.x_in),
-                    _p(pred), None, self.B, self.T, self.H, self.W, h["C"], h["Cout"], None if det else _p(seed))
-            self.steps[h["step"]] = (L.lfvdm_conv_out_update_x0, args)
-            self.head_fused = True
-            return True
-        if ddim is not None:
-            det = ddim["sigma"] is None
-            args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in),
-                    _p(noise) if inject_noise and not det else None, None if inject_noise or det else _p(noise), _p(t_buf),
-                    _p(tables["sqrt_recip_alphas_cumprod"]), _p(tables["sqrt_recipm1_alphas_cumprod"]), _p(ddim["k1"]),
-                    _p(ddim["k2"]), None if det else _p(ddim["sigma"]), int(bool(clip)), _p(self.x_in), _p(pred), self.B, self.T,
-                    self.H, self.W, h["C"], h["Cout"], None if det else _p(seed))
-            self.steps[h["step"]] = (L.lfvdm_conv_out_ddim, args)
-            self.head_fused = True
-            return True
-        args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in), _p(noise) if inject_noise else None,
-                None if inject_noise else _p(noise), _p(t_buf), _p(tables["sqrt_recip_alphas_cumprod"]),
-                _p(tables["sqrt_recipm1_alphas_cumprod"]), _p(tables["posterior_mean_coef1"]),
-                _p(tables["posterior_mean_coef2"]), _p(tables["model_log_variance"]), int(bool(clip)), _p(self.x_in), _p(pred),
-                None, self.B, self.T, self.H, self.W, h["C"], h["Cout"], _p(seed))
-        self.steps[h["step"]] = (L.lfvdm_conv_out_psample, args)
+        recip, recipm1, c1, c2, sg, rule, mean_type = update_args(tables, ddim, predict_xstart)
+        det, x0 = sg is None, recip is None
+        args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in),
+                _p(noise) if inject_noise and not det else None, None if inject_noise or det else _p(noise), _p(t_buf),
+                None if x0 else _p(recip), None if x0 else _p(recipm1), _p(c1), _p(c2), None if det else _p(sg), rule, mean_type,
+                int(bool(clip)), _p(self.x_in), _p(pred), None, self.B, self.T, self.H, self.W, h["C"], h["Cout"],
+                None if det else _p(seed))
+        self.steps[h["step"]] = (L.lfvdm_conv_out_update_x0, args)
         self.head_fused = True
         return True
 

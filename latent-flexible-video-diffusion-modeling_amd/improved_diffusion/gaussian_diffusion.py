@@ -14,7 +14,12 @@ What is native here
     mean type of the same kernels, chosen at compile time next to the rule: x0-hat is the clamped network output, the
     ``sqrt_recip`` / ``sqrt_recipm1`` tables are not read, everything behind x0-hat (posterior mean or folded DDIM rule,
     noise, the replayed step, the fused head launch) is shared with epsilon prediction, and ``training_losses`` regresses
-    on ``x_start``.
+    on ``x_start``;
+  * every update the package issues - eager (``_update``), replayed (``GraphSampler._step_body``) or fused into the output
+    convolution (``Plan.fuse_head_update``) - goes through the three general entries lfvdm_update_x0, lfvdm_update_rng_x0 and
+    lfvdm_conv_out_update_x0 with the arguments of ONE descriptor (``_update_args``: tables, rule, mean type).  The six older
+    entries (lfvdm_p_sample[_rng], lfvdm_ddim_sample[_rng], lfvdm_conv_out_psample, lfvdm_conv_out_ddim) launch the same
+    kernels and remain exported, bound and wrapped for users of the C ABI.
 
   * the variational bound (``use_kl=True`` training, ``_vb_terms_bpd``, ``_prior_bpd``, ``calc_bpd_loop[_subsampled]``,
     reference :687-720, :743-753, :798-888, losses.py) with fixed sigma: the KL / discretized-decoder term of a batch row,
@@ -260,36 +265,41 @@ class GaussianDiffusion:
         return self._predict_xstart_from_eps(x_t, t, model_output)
 
     # ------------------------------------------------------------------ p(x_{t-1} | x_t)
-    # ``eps`` below is the network's output: the noise, or x0-hat when ``predicts_xstart``
-    def _p_update(self, x, eps, t, noise, clip_denoised, want_mean=False):
-        tb = self.tables(x.device)
+    def _update_args(self, device, rule=("ancestral",), reverse=False):
+        """(recip, recipm1, c1, c2, sg, RULE_*, MEAN_*) of the update ``rule`` - ("ancestral",) or ("ddim", eta) - of this
+        model's mean type: what every update launch of the package is issued with (``_engine.update_args``)."""
+        from ._engine import update_args
+        ddim = self.ddim_tables(device, rule[1], reverse) if rule[0] == "ddim" else None
+        return update_args(self.tables(device), ddim, self.predicts_xstart)
+
+    # ``out`` below is the network's output: the noise, or x0-hat when ``predicts_xstart``
+    def _update(self, x, out, t, noise, clip_denoised, rule=("ancestral",), reverse=False, want_mean=False):
+        """One fused launch (lfvdm_update_x0) -> sample, x0-hat, and the mean on request.  ``noise`` None: the noise-free
+        call of ``p_mean_variance`` (the ancestral kernel wants a pointer: ``x`` stands in); a deterministic DDIM rule
+        reads no noise at all."""
+        recip, recipm1, c1, c2, sg, R, M = self._update_args(x.device, rule, reverse)
         sample = th.empty_like(x, memory_format=th.contiguous_format)
         pred = th.empty_like(sample)
         mean = th.empty_like(sample) if want_mean else None
-        if self.predicts_xstart:
-            nat.update_x0(x.contiguous(), eps.contiguous(), noise.contiguous() if noise is not None else x.contiguous(),
-                          t.to(th.int64).contiguous(), None, None, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
-                          tb["model_log_variance"], nat.RULE_ANCESTRAL, nat.MEAN_X0, clip_denoised, sample, pred, mean)
-            return sample, pred, mean
-        nat.p_sample(x.contiguous(), eps.contiguous(), noise.contiguous() if noise is not None else x.contiguous(),
-                     t.to(th.int64).contiguous(), tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"],
-                     tb["posterior_mean_coef1"], tb["posterior_mean_coef2"], tb["model_log_variance"], clip_denoised,
-                     sample, pred, mean)
+        z = None if sg is None else (noise if noise is not None else x).contiguous()
+        nat.update_x0(x.contiguous(), out.contiguous(), z, t.to(th.int64).contiguous(), recip, recipm1, c1, c2, sg, R, M,
+                      clip_denoised, sample, pred, mean)
         return sample, pred, mean
 
-    def _p_update_denoised(self, x, eps, t, noise, clip_denoised, denoised_fn):
+    def _update_denoised(self, x, out, t, noise, clip_denoised, denoised_fn, rule=("ancestral",), reverse=False):
         """The same update with a user function applied to x0-hat before clipping (reference process_xstart,
         :305-309).  ``denoised_fn`` is arbitrary Python on a tensor, so this rarely used variant is composed of
-        elementwise device ops around it instead of the fused kernel."""
+        elementwise device ops around it instead of the fused kernel:  c1[t] * p0 + c2[t] * x + [t != 0] * sigma[t] * z."""
         n = x.dim()
-        pred = denoised_fn(self._xstart_from_output(x, t, eps))
+        pred = denoised_fn(self._xstart_from_output(x, t, out))
         if clip_denoised:
             pred = pred.clamp(-1, 1)
-        mean, _, _ = self.q_posterior_mean_variance(pred, x, t)
-        if noise is None:
+        _, _, c1, c2, sg, R, _ = self._update_args(x.device, rule, reverse)
+        mean = _bshape(c1[t], n) * pred + _bshape(c2[t], n) * x
+        if sg is None or noise is None:
             return mean, pred, mean
-        nonzero = _bshape((t != 0).to(x.dtype), n)       # no noise at t == 0 (reference :397-399)
-        sample = mean + nonzero * th.exp(0.5 * self._gather("model_log_variance", t, n)) * noise
+        sigma = th.exp(0.5 * sg[t]) if R == nat.RULE_ANCESTRAL else sg[t]      # the ancestral table holds log variances
+        sample = mean + _bshape((t != 0).to(x.dtype) * sigma, n) * noise        # no noise at t == 0 (reference :397-399)
         return sample, pred, mean
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None,
@@ -301,9 +311,9 @@ class GaussianDiffusion:
         assert t.shape == (B,)
         eps, attn = model(x, self._scale_timesteps(t), return_attn_weights=return_attn_weights, **model_kwargs)
         if denoised_fn is not None:
-            _, pred, mean = self._p_update_denoised(x, eps, t, None, clip_denoised, denoised_fn)
+            _, pred, mean = self._update_denoised(x, eps, t, None, clip_denoised, denoised_fn)
         else:   # noise-free update: the kernel returns the posterior mean and x0-hat in one pass
-            _, pred, mean = self._p_update(x, eps, t, None, clip_denoised, want_mean=True)
+            _, pred, mean = self._update(x, eps, t, None, clip_denoised, want_mean=True)
         n = x.dim()
         return {"mean": mean, "variance": self._gather("model_variance", t, n).expand(x.shape),
                 "log_variance": self._gather("model_log_variance", t, n).expand(x.shape),
@@ -319,9 +329,9 @@ class GaussianDiffusion:
         if noise is None:
             noise = th.randn_like(x)
         if denoised_fn is not None:
-            sample, pred, _ = self._p_update_denoised(x, eps, t, noise, clip_denoised, denoised_fn)
+            sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn)
         else:
-            sample, pred, _ = self._p_update(x, eps, t, noise, clip_denoised)
+            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised)
         return {"sample": sample, "pred_xstart": pred, "attn": attn}
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
@@ -368,7 +378,15 @@ class GaussianDiffusion:
         On the MI355X the step is one hipGraph replay (``GraphSampler``); yielded tensors are fresh
         copies unless the internal ``_reuse_buffers`` flag is set by ``p_sample_loop``.  Unlike the
         reference, grad mode is never left disabled when the generator is abandoned early."""
+        return self._sample_loop(("ancestral",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress,
+                                 return_attn_weights, _reuse_buffers, _final_only)
+
+    def _sample_loop(self, rule, model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress,
+                     return_attn_weights=False, _reuse_buffers=False, _final_only=False):
+        """The chain of either rule - ("ancestral",) or ("ddim", eta) - behind both progressive loops; the dicts of the
+        ancestral chain carry ``attn`` as those of ``p_sample`` do."""
         from .unet import UNetVideoModel
+        keys = ("sample", "pred_xstart", "attn") if rule[0] == "ancestral" else ("sample", "pred_xstart")
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
@@ -382,21 +400,21 @@ class GaussianDiffusion:
         fast = (isinstance(inner, UNetVideoModel) and img.is_cuda and denoised_fn is None
                 and not return_attn_weights and model_kwargs is not None)
         if fast:
-            sampler = self._graph_sampler(inner, tuple(shape), clip_denoised)
+            sampler = self._graph_sampler(inner, tuple(shape), clip_denoised, rule=rule)
             sampler.begin(img, model_kwargs)
-            if _final_only and not progress:      # p_sample_loop: nobody looks at the intermediate states
+            if _final_only and not progress:      # [p|ddim]_sample_loop: nobody looks at the intermediate states
                 out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
                 if sampler.chain_timed_out():     # a persistent level chain gave up a wait: the samples are garbage
                     sampler.fall_back()           # (said on stderr) -> one launch per stage, and the chain again
                     sampler.begin(img, model_kwargs)
                     out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
-                yield out
+                yield {k: out[k] for k in keys}
                 return
             for n, i in enumerate(indices):
                 out = sampler.step(i)
                 # a persistent level chain that gave up a wait leaves garbage behind and its abort word is sticky: every
                 # later step of this chain would abort as well.  The states already yielded cannot be taken back, so this
-                # path RAISES (checked every 64 steps and behind the last one; p_sample_loop's final-only path reruns the
+                # path RAISES (checked every 64 steps and behind the last one; the final-only path above reruns the
                 # chain instead) - after switching the plan to one launch per stage, so that the caller's retry works
                 if (n & 63) == 63 or i == 0:
                     if sampler.chain_timed_out():
@@ -404,46 +422,21 @@ class GaussianDiffusion:
                         raise RuntimeError("a persistent level chain timed out during this sampling chain (lfvdm_level_chain): "
                                            "the states yielded since the last check are not valid; the plan now runs one "
                                            "launch per stage - run the chain again")
-                if not _reuse_buffers:
-                    out = {k: (v.clone() if isinstance(v, th.Tensor) else v) for k, v in out.items()}
-                yield out
+                yield {k: (out[k] if _reuse_buffers or out[k] is None else out[k].clone()) for k in keys}
             return
         for i in indices:
             t = th.full((shape[0],), i, device=device, dtype=th.long)
             with th.no_grad():
-                out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                    model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
+                if rule[0] == "ancestral":
+                    out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                        model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
+                else:
+                    out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                           model_kwargs=model_kwargs, eta=rule[1])
             yield out
             img = out["sample"]
 
     # ------------------------------------------------------------------ DDIM (reference :524-685)
-    def _ddim_update(self, x, eps, t, noise, clip_denoised, eta, reverse=False):
-        tb, co = self.tables(x.device), self.ddim_tables(x.device, eta, reverse)
-        sample = th.empty_like(x, memory_format=th.contiguous_format)
-        pred = th.empty_like(sample)
-        if self.predicts_xstart:    # the folded rule is written in terms of x0-hat: the same k1 / k2 / sigma
-            nat.update_x0(x.contiguous(), eps.contiguous(), noise.contiguous() if co["sigma"] is not None else None,
-                          t.to(th.int64).contiguous(), None, None, co["k1"], co["k2"], co["sigma"], nat.RULE_DDIM, nat.MEAN_X0,
-                          clip_denoised, sample, pred)
-            return sample, pred
-        nat.ddim_sample(x.contiguous(), eps.contiguous(), noise.contiguous() if co["sigma"] is not None else None,
-                        t.to(th.int64).contiguous(), tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"],
-                        co["k1"], co["k2"], co["sigma"], clip_denoised, sample, pred)
-        return sample, pred
-
-    def _ddim_update_denoised(self, x, eps, t, noise, clip_denoised, denoised_fn, eta, reverse=False):
-        """The two-launch route of ``_p_update_denoised`` for DDIM: x0-hat, the user's function, the clamp, then the folded
-        rule as elementwise device ops."""
-        n = x.dim()
-        pred = denoised_fn(self._xstart_from_output(x, t, eps))
-        if clip_denoised:
-            pred = pred.clamp(-1, 1)
-        co = self.ddim_tables(x.device, eta, reverse)
-        sample = _bshape(co["k1"][t], n) * pred + _bshape(co["k2"][t], n) * x
-        if co["sigma"] is not None:
-            sample = sample + _bshape((t != 0).to(x.dtype) * co["sigma"][t], n) * noise
-        return sample, pred
-
     def _ddim_step(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, reverse, noise=None):
         self._check_native_modes()
         model_kwargs = model_kwargs or {}
@@ -452,9 +445,9 @@ class GaussianDiffusion:
         if float(eta) != 0.0 and noise is None:
             noise = th.randn_like(x)
         if denoised_fn is not None:
-            sample, pred = self._ddim_update_denoised(x, eps, t, noise, clip_denoised, denoised_fn, eta, reverse)
+            sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn, ("ddim", eta), reverse)
         else:
-            sample, pred = self._ddim_update(x, eps, t, noise, clip_denoised, eta, reverse)
+            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised, ("ddim", eta), reverse)
         return {"sample": sample, "pred_xstart": pred}
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, noise=None):
@@ -479,8 +472,8 @@ class GaussianDiffusion:
             raise NotImplementedError("ddim_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); pass "
                                       "return_decoded=False for latents - refused BEFORE the chain runs")
         final = None
-        for sample in self._ddim_loop(model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress, eta,
-                                      _reuse_buffers=True, _final_only=True):
+        for sample in self._sample_loop(("ddim", float(eta)), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
+                                        progress, _reuse_buffers=True, _final_only=True):
             final = sample
         out = final["sample"].clone()
         return self.decode(out) if return_decoded else out
@@ -489,50 +482,8 @@ class GaussianDiffusion:
                                      device=None, progress=False, eta=0.0):
         """Generator over the dicts of ``ddim_sample`` for t = T-1 .. 0 (reference :644-685); replayed through
         ``GraphSampler`` under the conditions of ``p_sample_loop_progressive``."""
-        return self._ddim_loop(model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress, eta)
-
-    def _ddim_loop(self, model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress, eta,
-                   _reuse_buffers=False, _final_only=False):
-        from .unet import UNetVideoModel
-        if device is None:
-            device = next(model.parameters()).device
-        assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        indices = list(range(self.num_timesteps))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        inner = getattr(model, "model", model)  # _WrappedModel -> module
-        inner = getattr(inner, "module", inner)  # DDP -> module
-        fast = isinstance(inner, UNetVideoModel) and img.is_cuda and denoised_fn is None and model_kwargs is not None
-        if fast:
-            sampler = self._graph_sampler(inner, tuple(shape), clip_denoised, rule=("ddim", float(eta)))
-            sampler.begin(img, model_kwargs)
-            if _final_only and not progress:
-                out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
-                if sampler.chain_timed_out():     # as p_sample_loop: the samples are garbage -> one launch per stage, again
-                    sampler.fall_back()
-                    sampler.begin(img, model_kwargs)
-                    out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
-                yield {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
-                return
-            for n, i in enumerate(indices):
-                out = sampler.step(i)
-                if (n & 63) == 63 or i == 0:      # see p_sample_loop_progressive
-                    if sampler.chain_timed_out():
-                        sampler.fall_back()
-                        raise RuntimeError("a persistent level chain timed out during this sampling chain (lfvdm_level_chain): "
-                                           "the states yielded since the last check are not valid; the plan now runs one "
-                                           "launch per stage - run the chain again")
-                yield {k: (out[k] if _reuse_buffers else out[k].clone()) for k in ("sample", "pred_xstart")}
-            return
-        for i in indices:
-            t = th.full((shape[0],), i, device=device, dtype=th.long)
-            with th.no_grad():
-                out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                       model_kwargs=model_kwargs, eta=eta)
-            yield out
-            img = out["sample"]
+        return self._sample_loop(("ddim", float(eta)), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
+                                 progress)
 
     def _graph_sampler(self, unet, shape, clip_denoised, rule=("ancestral",)):
         # the update rule is part of the key (appended: position 1 stays the shape): a DDIM chain and an ancestral chain on
@@ -797,28 +748,25 @@ class GaussianDiffusion:
         return frames.unflatten(0, (B, T)).to(video.device).to(out_dtype)
 
 
-class GraphSampler:
-    """One denoising step (timestep remap -> U-Net forward -> noise -> x_{t-1} update -> t -= 1)
-    captured as a hipGraph over the engine's static buffers; ``step`` is a single replay."""
+class ReplayedStep:
+    """One step of a chain over a private plan, captured as a hipGraph over the plan's static buffers: what the sampler and
+    the bits-per-dim evaluator share.  The plan and its timestep tables, the device-side clock ``t_buf``, the per-chain
+    table build, the warm-up and capture of ``_step_body`` (the subclass's), the chain-timeout check and the fall-back,
+    and ``step``: a single replay."""
 
-    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False, rule=("ancestral",)):
+    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise):
         # inject_noise (parity tests): the replayed step READS ``self.noise`` - the caller fills it before every
         # ``step`` - instead of drawing it (the reference's th.randn_like, gaussian_diffusion.py:396)
-        # rule: ("ancestral",) or ("ddim", eta) - which update closes the step; fixed for the life of the captured graphs
         self.diffusion, self.unet, self.shape = diffusion, unet, tuple(shape)
         self.clip = bool(clip_denoised)
         self.inject_noise = bool(inject_noise)
-        self.rule = tuple(rule)
-        if self.rule[0] not in ("ancestral", "ddim") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
-            raise ValueError(f"unknown update rule {rule!r}")
-        self.ddim = None                # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic)
         diffusion._check_native_modes()
-        # the mean type is fixed for the life of the captured graphs, as the rule is (``_samplers`` lives on the diffusion
-        # object: it needs no key element).  Not to be confused with model_kwargs["x0"], the conditioning frames
+        # the mean type is fixed for the life of the captured graphs (the caches live on the diffusion object: they need
+        # no key element).  Not to be confused with model_kwargs["x0"], the conditioning frames
         self.x0_mode = diffusion.predicts_xstart
         B, T, Cx, H, W = self.shape
         from ._engine import Plan
-        # a private plan: the sampler's state lives in its static buffers, so it must not be shared
+        # a private plan: the chain's state lives in its static buffers, so it must not be shared
         # with eager model() calls on the same shape
         self.engine = unet.native_engine()
         # the chain walks a known schedule: everything that depends on (t, frame_indices) alone is tabulated once per
@@ -827,28 +775,14 @@ class GraphSampler:
         self.plan.refresh_weights()
         dev = self.plan.dev
         self.tb = diffusion.tables(dev)
-        if self.rule[0] == "ddim":
-            self.ddim = diffusion.ddim_tables(dev, self.rule[1])
         self.ts_table = diffusion.model_timestep_table(dev)
         self.t_buf = self.plan.t_sel if self.plan.time_steps else th.zeros(B, dtype=th.int64, device=dev)
         self._table_events = None      # (start, end) events around the table build of the last begin()
         self._ts_key = tuple(self.ts_table.tolist())
-        self.noise = th.empty(self.shape, device=dev)
-        self.pred = th.empty(self.shape, device=dev)
-        # the replayed step draws its noise inside the update kernel (lfvdm_p_sample_rng: Philox keyed by a per-chain seed
-        # that begin() takes from torch's generator, so th.manual_seed still fixes the video); LFVDM_SAMPLER_NOISE=torch
-        # keeps the th.randn launch
-        self.seed = th.zeros(1, dtype=th.int64, device=dev)
         self.graph = None
-        # consecutive steps of a chain are also captured K at a time (``run``): a graph launch costs the GPU ~18 us whatever
-        # it holds (1063 -> 1080 steps/s at cfg B with 8 steps per launch; 32 and more lose again); LFVDM_STEPS_PER_GRAPH=1: off
-        import os
-        self.K = max(1, int(os.environ.get("LFVDM_STEPS_PER_GRAPH", "8")))
-        if self.plan.time_steps and self.plan.time_ring:
-            self.K = min(self.K, self.plan.time_ring // 2)     # a graph launch must not walk more than half the R ring
-        self.graph_k = None
         self.expected_t = None
         self._abort_unchecked = False       # steps have run since the chains' abort words were last read
+        self.chain_timeouts = 0
 
     @property
     def table_build_ms(self):
@@ -858,71 +792,6 @@ class GraphSampler:
         e0, e1 = self._table_events
         e1.synchronize()
         return e0.elapsed_time(e1)
-
-    def _step_body(self):
-        import os
-        pl, tb = self.plan, self.tb
-
-        def tick():     # device-side clock: t <- max(t - 1, 0), model timestep <- table[t]  (t_buf holds "previous t");
-            pl.tick(self.t_buf, self.ts_table)      # with timestep tables it also fetches the FiLM rows of the new t
-
-        # the x_{t-1} update rides in the plan's last launch (output conv + update: lfvdm_conv_out_psample) where the
-        # shape allows; LFVDM_FUSED_HEAD=0 keeps the two launches (A/B aid)
-        dd = self.ddim
-        det = dd is not None and dd["sigma"] is None       # eta = 0: no noise of any kind, whatever the noise settings say
-        fused = (os.environ.get("LFVDM_FUSED_HEAD", "1") != "0"
-                 and (det or self.inject_noise or os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
-                 and pl.fuse_head_update(self.t_buf, tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
-                                         ddim=dd, predict_xstart=self.x0_mode))
-        if pl.time_steps and os.environ.get("LFVDM_TICK_IN_CONV", "1") != "0":
-            pl.launch(tick=(self.t_buf, self.ts_table))      # the clock rides in the first launch of the forward
-            self.extra_launches = 1                           # (the update; bench.py reports launches per step)
-        else:
-            tick()
-            pl.launch()
-            self.extra_launches = 2
-        if fused:
-            self.extra_launches -= 1
-            return
-        if self.x0_mode:      # the three stand-alone updates of an x0-prediction model: the same launches, MEAN_X0
-            if dd is not None:
-                c1, c2, sg, rule = dd["k1"], dd["k2"], dd["sigma"], nat.RULE_DDIM
-            else:
-                c1, c2, sg = tb["posterior_mean_coef1"], tb["posterior_mean_coef2"], tb["model_log_variance"]
-                rule = nat.RULE_ANCESTRAL
-            if det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch"):
-                nat.update_rng_x0(pl.x_in, pl.out, None if det else self.noise, self.t_buf, None, None, c1, c2, sg, rule,
-                                  nat.MEAN_X0, self.clip, pl.x_in, None if det else self.seed, self.pred)
-                return
-            if not self.inject_noise:
-                self.extra_launches = getattr(self, "extra_launches", 2) + 1
-                self.noise.normal_()
-            nat.update_x0(pl.x_in, pl.out, self.noise, self.t_buf, None, None, c1, c2, sg, rule, nat.MEAN_X0, self.clip, pl.x_in,
-                          self.pred)
-            return
-        if dd is not None:
-            recip, recipm1 = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
-            if det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch"):
-                nat.ddim_sample_rng(pl.x_in, pl.out, None if det else self.noise, self.t_buf, recip, recipm1, dd["k1"], dd["k2"],
-                                    dd["sigma"], self.clip, pl.x_in, None if det else self.seed, self.pred)
-                return
-            if not self.inject_noise:
-                self.extra_launches = getattr(self, "extra_launches", 2) + 1
-                self.noise.normal_()
-            nat.ddim_sample(pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, dd["k1"], dd["k2"], dd["sigma"], self.clip,
-                            pl.x_in, self.pred)
-            return
-        if not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch":
-            nat.p_sample_rng(pl.x_in, pl.out, self.noise, self.t_buf, tb["sqrt_recip_alphas_cumprod"],
-                             tb["sqrt_recipm1_alphas_cumprod"], tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
-                             tb["model_log_variance"], self.clip, pl.x_in, self.seed, self.pred, None)
-            return
-        if not self.inject_noise:
-            self.extra_launches = getattr(self, "extra_launches", 2) + 1
-            self.noise.normal_()
-        nat.p_sample(pl.x_in, pl.out, self.noise, self.t_buf, tb["sqrt_recip_alphas_cumprod"],
-                     tb["sqrt_recipm1_alphas_cumprod"], tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
-                     tb["model_log_variance"], self.clip, pl.x_in, self.pred, None)
 
     def _build_chain_tables(self, frame_indices):
         """Once per chain, plan with timestep tables: the FiLM rows (once per set of weights), this window's R tables, the
@@ -971,23 +840,18 @@ class GraphSampler:
         th.cuda.synchronize()
         th.cuda.set_rng_state(rng_state, pl.dev)
 
-    def begin(self, img, model_kwargs):
+    def _begin_chain(self, x, model_kwargs):
+        """``x`` becomes the plan's input; this chain's tables; the graph (first chain only); the clock on the top."""
         pl = self.plan
-        B, T = pl.B, pl.T
-        # callers that drive step() / run() themselves: checked once per chain, here - unless whoever ran the previous
-        # chain has looked already (p_sample_loop does, behind run(): one host synchronisation per chain, not two)
-        if self._abort_unchecked and self.chain_timed_out():
-            self.fall_back()
         if pl._sig != pl.weight_signature():
             pl.refresh_weights()  # parameters changed since the last chain
         with th.no_grad():
-            pl.set_inputs(img, model_kwargs["x0"], th.zeros(B, device=pl.dev), model_kwargs["frame_indices"],
+            pl.set_inputs(x, model_kwargs["x0"], th.zeros(pl.B, device=pl.dev), model_kwargs["frame_indices"],
                           model_kwargs["obs_mask"], model_kwargs["latent_mask"])
             self._build_chain_tables(model_kwargs["frame_indices"])
             if self.graph is None:
                 self._capture_step()
             self.t_buf.fill_(self.diffusion.num_timesteps)     # the step pre-decrements
-            self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
         self.expected_t = self.diffusion.num_timesteps - 1
 
     def chain_timed_out(self):
@@ -997,14 +861,97 @@ class GraphSampler:
         return bool(self.plan.chains) and self.plan.chains_aborted()
 
     def fall_back(self):
-        """After a chain timeout: the samples of the chain that just ran are not to be trusted.  Say so, run this plan one
-        launch per stage from now on, and have the step graphs captured again."""
+        """After a chain timeout: the results of the chain that just ran are not to be trusted.  Say so, run this plan one
+        launch per stage from now on, and have the step graph captured again."""
         import sys
         print("[lfvdm] ERROR: a persistent level chain timed out (lfvdm_level_chain); falling back to the per-launch plan",
               file=sys.stderr, flush=True)
         self.plan.disable_chains()
-        self.graph = self.graph_k = None
-        self.chain_timeouts = getattr(self, "chain_timeouts", 0) + 1
+        self.graph = None
+        self.chain_timeouts += 1
+
+    def step(self, i):
+        if i != self.expected_t:  # arbitrary order requested: reset the device-side counter
+            self.t_buf.fill_(i + 1)
+        self.plan.ensure_R(i)
+        self.graph.replay()
+        self._abort_unchecked = True
+        self.expected_t = max(i - 1, 0)
+
+
+class GraphSampler(ReplayedStep):
+    """One denoising step (timestep remap -> U-Net forward -> noise -> x_{t-1} update -> t -= 1)
+    captured as a hipGraph over the engine's static buffers; ``step`` is a single replay."""
+
+    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False, rule=("ancestral",)):
+        # rule: ("ancestral",) or ("ddim", eta) - which update closes the step; fixed for the life of the captured graphs
+        self.rule = tuple(rule)
+        if self.rule[0] not in ("ancestral", "ddim") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
+            raise ValueError(f"unknown update rule {rule!r}")
+        super().__init__(diffusion, unet, shape, clip_denoised, inject_noise)
+        dev = self.plan.dev
+        # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic), and what the update is launched with
+        self.ddim = diffusion.ddim_tables(dev, self.rule[1]) if self.rule[0] == "ddim" else None
+        self.update = diffusion._update_args(dev, self.rule)
+        self.noise = th.empty(self.shape, device=dev)
+        self.pred = th.empty(self.shape, device=dev)
+        # the replayed step draws its noise inside the update kernel (lfvdm_update_rng_x0: Philox keyed by a per-chain seed
+        # that begin() takes from torch's generator, so th.manual_seed still fixes the video); LFVDM_SAMPLER_NOISE=torch
+        # keeps the th.randn launch
+        self.seed = th.zeros(1, dtype=th.int64, device=dev)
+        # consecutive steps of a chain are also captured K at a time (``run``): a graph launch costs the GPU ~18 us whatever
+        # it holds (1063 -> 1080 steps/s at cfg B with 8 steps per launch; 32 and more lose again); LFVDM_STEPS_PER_GRAPH=1: off
+        import os
+        self.K = max(1, int(os.environ.get("LFVDM_STEPS_PER_GRAPH", "8")))
+        if self.plan.time_steps and self.plan.time_ring:
+            self.K = min(self.K, self.plan.time_ring // 2)     # a graph launch must not walk more than half the R ring
+        self.graph_k = None
+
+    def _step_body(self):
+        """The clock and the forward, then at most one update launch, chosen by where the noise comes from."""
+        import os
+        pl = self.plan
+        recip, recipm1, c1, c2, sg, rule, mean_type = self.update
+        det = sg is None        # DDIM with eta = 0: no noise of any kind, whatever the noise settings say
+        in_kernel = det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
+        # the x_{t-1} update rides in the plan's last launch (output conv + update: lfvdm_conv_out_update_x0) where the
+        # shape allows; LFVDM_FUSED_HEAD=0 keeps the two launches (A/B aid)
+        fused = (os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
+                 and pl.fuse_head_update(self.t_buf, self.tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
+                                         ddim=self.ddim, predict_xstart=self.x0_mode))
+        # device-side clock: t <- max(t - 1, 0), model timestep <- table[t]  (t_buf holds "previous t"); with timestep
+        # tables it also fetches the FiLM rows of the new t, and rides in the first launch of the forward
+        tick_in_conv = bool(pl.time_steps) and os.environ.get("LFVDM_TICK_IN_CONV", "1") != "0"
+        if tick_in_conv:
+            pl.launch(tick=(self.t_buf, self.ts_table))
+        else:
+            pl.tick(self.t_buf, self.ts_table)
+            pl.launch()
+        draw = not (fused or in_kernel or self.inject_noise)
+        # launches of a step beside the plan's own (bench.py reports launches per step): the clock, the update, the draw
+        self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw)
+        if fused:
+            return
+        if in_kernel:
+            nat.update_rng_x0(pl.x_in, pl.out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
+                              mean_type, self.clip, pl.x_in, None if det else self.seed, self.pred)
+            return
+        if draw:
+            self.noise.normal_()
+        nat.update_x0(pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, self.clip, pl.x_in,
+                      self.pred)
+
+    def begin(self, img, model_kwargs):
+        # callers that drive step() / run() themselves: checked once per chain, here - unless whoever ran the previous
+        # chain has looked already (p_sample_loop does, behind run(): one host synchronisation per chain, not two)
+        if self._abort_unchecked and self.chain_timed_out():
+            self.fall_back()
+        self._begin_chain(img, model_kwargs)
+        self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
+
+    def fall_back(self):
+        super().fall_back()
+        self.graph_k = None
 
     def chain_table_ms(self):
         """GPU milliseconds of ALL table building of one chain of this sampler (every R block once; the FiLM rows are per
@@ -1023,14 +970,12 @@ class GraphSampler:
             pl.ensure_R(self.expected_t)
         return e0.elapsed_time(e1)
 
-    def step(self, i):
-        if i != self.expected_t:  # arbitrary order requested: reset the device-side counter
-            self.t_buf.fill_(i + 1)
-        self.plan.ensure_R(i)
-        self.graph.replay()
-        self._abort_unchecked = True
-        self.expected_t = max(i - 1, 0)
+    def _state(self):
         return {"sample": self.plan.x_in, "pred_xstart": self.pred, "attn": None}
+
+    def step(self, i):
+        super().step(i)
+        return self._state()
 
     def run(self, i, n):
         """``n`` consecutive steps t = i, i-1, ... (the clock stops at 0): exactly ``step`` n times - the noise is keyed by
@@ -1059,46 +1004,24 @@ class GraphSampler:
             t = max(t - 1, 0)
         self._abort_unchecked = True
         self.expected_t = max(int(i) - int(n), 0)
-        return {"sample": self.plan.x_in, "pred_xstart": self.pred, "attn": None}
+        return self._state()
 
 
-class BpdEvaluator(GraphSampler):
+class BpdEvaluator(ReplayedStep):
     """One evaluation step of ``calc_bpd_loop`` (clock tick -> noise draw -> q_sample into the plan's input -> U-Net forward
     -> lfvdm_vb_terms into column j of the (N, T) results) captured as a hipGraph over a private plan with timestep
-    tables; ``step`` is a single replay.  The table build, the warm-up and capture, the chain-timeout check and the
-    fall-back are ``GraphSampler``'s; the step body, its buffers and ``begin`` are its own.  The column index is derived on
-    the device from the clock (num_timesteps - 1 - t)."""
+    tables; ``step(i)`` - a single replay - writes the term of timestep ``i`` to column num_timesteps - 1 - i of ``vb`` /
+    ``xstart_mse`` / ``mse``: the column index is derived on the device from the clock."""
 
     def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False):
-        # inject_noise (parity tests): the replayed step READS ``self.noise`` - the caller fills it before every ``step``
-        self.diffusion, self.unet, self.shape = diffusion, unet, tuple(shape)
-        self.clip = bool(clip_denoised)
-        self.inject_noise = bool(inject_noise)
-        diffusion._check_native_modes()
-        self.x0_mode = diffusion.predicts_xstart
-        B, T, Cx, H, W = self.shape
-        from ._engine import Plan
-        self.engine = unet.native_engine()
-        self.plan = Plan(self.engine, B, T, H, W, False, time_steps=diffusion.num_timesteps)
-        self.plan.refresh_weights()
-        dev = self.plan.dev
-        self.tb = diffusion.tables(dev)
-        self.ts_table = diffusion.model_timestep_table(dev)
-        self._ts_key = tuple(self.ts_table.tolist())
-        self._table_events = None
-        # the evaluator always walks with timestep tables (GraphSampler also serves plans without them); what the inherited
-        # _build_chain_tables / _capture_step / chain_timed_out / fall_back read is set below, nothing else of the sampler
+        super().__init__(diffusion, unet, shape, clip_denoised, inject_noise)
+        # the evaluator always walks with timestep tables (the sampler also serves plans without them)
         assert self.plan.time_steps == diffusion.num_timesteps and self.plan.t_sel is not None
-        self.t_buf = self.plan.t_sel
-        n = diffusion.num_timesteps
+        B, T, n, dev = self.plan.B, self.plan.T, diffusion.num_timesteps, self.plan.dev
         self.x_start = th.empty(self.shape, device=dev)
         self.noise = th.empty(self.shape, device=dev)
         self.mask = th.ones(B, T, device=dev)
         self.vb, self.xstart_mse, self.mse = (th.zeros(B, n, device=dev) for _ in range(3))
-        self.graph = self.graph_k = None
-        self.expected_t = None
-        self._abort_unchecked = False
-        self.chain_timeouts = 0
 
     def _step_body(self):
         pl, tb, d = self.plan, self.tb, self.diffusion
@@ -1113,35 +1036,13 @@ class BpdEvaluator(GraphSampler):
                      col_base=d.num_timesteps - 1)
 
     def begin(self, x_start, model_kwargs, latent_mask=None):
-        pl = self.plan
-        B, T = pl.B, pl.T
-        if pl._sig != pl.weight_signature():
-            pl.refresh_weights()
         with th.no_grad():
             self.x_start.copy_(x_start)
             if latent_mask is None:
                 self.mask.fill_(1.0)
             else:
-                self.mask.copy_(latent_mask.reshape(B, T))
-            pl.set_inputs(self.x_start, model_kwargs["x0"], th.zeros(B, device=pl.dev), model_kwargs["frame_indices"],
-                          model_kwargs["obs_mask"], model_kwargs["latent_mask"])
-            self._build_chain_tables(model_kwargs["frame_indices"])
-            if self.graph is None:
-                self._capture_step()
-            self.t_buf.fill_(self.diffusion.num_timesteps)      # the step pre-decrements
-        self.expected_t = self.diffusion.num_timesteps - 1
-
-    def step(self, i):
-        """The term of timestep ``i`` -> column num_timesteps - 1 - i of ``vb`` / ``xstart_mse`` / ``mse``."""
-        if i != self.expected_t:
-            self.t_buf.fill_(i + 1)
-        self.plan.ensure_R(i)
-        self.graph.replay()
-        self._abort_unchecked = True
-        self.expected_t = max(i - 1, 0)
-
-    def run(self, i, n):
-        raise NotImplementedError("the evaluator walks one step per replay: use step() / evaluate()")
+                self.mask.copy_(latent_mask.reshape(self.mask.shape))
+        self._begin_chain(self.x_start, model_kwargs)
 
     def evaluate(self, x_start, model_kwargs, latent_mask=None):
         """Every timestep, descending -> fresh (N, T) copies of vb, xstart_mse, mse.  A persistent level chain that gave

@@ -268,7 +268,7 @@ def test_replayed_ddim10_chain_follows_the_reference_trajectory(config, monkeypa
 
 
 def test_eager_ddim10_chain_follows_the_reference_and_the_replayed_chain():
-    """The eager ddim_sample loop (model call + lfvdm_ddim_sample per step) against the same fixtures and bounds, and against
+    """The eager ddim_sample loop (model call + lfvdm_update_x0 per step) against the same fixtures and bounds, and against
     the replayed chain (two fp32 evaluations of one trajectory: twice the per-step bound)."""
     g = np.load(os.path.join(GOLDEN, "ddim_traj_cfgB_eta0.npz"))
     model, d, mk, shape = cfgB()

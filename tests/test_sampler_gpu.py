@@ -303,7 +303,7 @@ def test_replayed_sampler_at_32x32_and_nonsquare_latents_follows_the_reference_t
 
 
 def test_fused_head_chain_equals_the_two_launch_chain(monkeypatch):
-    """cfg-B sampler with the output conv + update in one launch (lfvdm_conv_out_psample, the default) against the same
+    """cfg-B sampler with the output conv + update in one launch (lfvdm_conv_out_update_x0, the default) against the same
     chain with the two launches (LFVDM_FUSED_HEAD=0): same noise stream (same chain seed), so the only difference is the
     summation order inside the 64 -> 4 convolution - the samples of 12 steps stay within 2e-5."""
     from improved_diffusion.gaussian_diffusion import GraphSampler
