@@ -44,6 +44,8 @@ extern "C" {
 #define LFVDM_OUT_ROWS 0 /* out[m*ldo + co]                        (channels-last rows) */
 #define LFVDM_OUT_NCHW 1 /* out[(n*Cout + co)*Ho*Wo + pix]          (reference frame layout) */
 
+/* Versions the launch-code encoding and the struct layouts below (what tuning caches and profile stamps are keyed on), not
+ * the list of entry points: a binding that names an entry this library lacks already fails when it resolves its symbols. */
 int lfvdm_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------
@@ -524,62 +526,39 @@ int lfvdm_attn_temporal_bwd(const float* qkv, const float* d_o, const float* Rq,
 /* q_sample, :200-218 */
 int lfvdm_q_sample(const float* x0, const float* noise, const int64_t* t, const float* sqrt_acp,
                    const float* sqrt_1macp, float* out, int B, int inner, void* stream);
-/* p_mean_variance (eps, fixed variance) + p_sample update, :290-346,369-401.
- * pred_xstart / mean_out may be NULL. */
-int lfvdm_p_sample(const float* x, const float* eps, const float* noise, const int64_t* t,
-                   const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* coef1,
-                   const float* coef2, const float* log_var, int clip, float* sample, float* pred_xstart,
-                   float* mean_out, int B, int inner, void* stream);
-/* The same update with the noise drawn INSIDE the kernel (the sampler's replayed step: one launch less than
- * th.randn + lfvdm_p_sample): Philox4x32-10 keyed by seed[0] (device int64, one value per chain), counter = (element quad,
- * batch row, timestep t[b]) -> Box-Muller; a (seed, timestep, element) triple always gives the same value.  noise_out
- * (optional) receives the standard normal values that were used. */
-int lfvdm_p_sample_rng(const float* x, const float* eps, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
-                       const float* sqrt_recipm1_acp, const float* coef1, const float* coef2, const float* log_var,
-                       int clip, float* sample, float* pred_xstart, float* mean_out, int B, int inner,
-                       const int64_t* seed, void* stream);
-/* The U-Net's 3x3 output convolution (unet.py:399-403,462-464) and the update above in ONE launch - the last two
- * launches of a replayed sampling step: eps = conv(act) + bias from the channels-last rows act [B*T*H*W][C] = SiLU(GN(h))
- * and the packed filters Wp [Cout][9][C] (lfvdm_pack_conv_weight), then lfvdm_p_sample_rng's arithmetic with the same
- * noise stream (noise_in != NULL: that noise instead, seed unused).  eps_out / noise_out / pred_xstart / mean_out may be
- * NULL; x and sample may alias.  _ok: 0 if the shape is covered (Cout 3 or 4, C 64 / 128 / 256, W % 4 == 0). */
-int lfvdm_conv_out_psample_ok(int N, int H, int W, int C, int Cout);
-int lfvdm_conv_out_psample(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
-                           const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
-                           const float* sqrt_recipm1_acp, const float* coef1, const float* coef2, const float* log_var,
-                           int clip, float* sample, float* pred_xstart, float* mean_out, int B, int T, int H, int W, int C,
-                           int Cout, const int64_t* seed, void* stream);
-/* DDIM (gaussian_diffusion.py:524-610: ddim_sample, ddim_reverse_sample) as a second update rule of the three update
- * kernels above, selected at compile time.  With p0 = clamp(sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] eps):
- *     sample = k1[t] p0 + k2[t] x + [t != 0] sigma[t] z
- * k1, k2, sigma are per-timestep fp32 tables folded on the host in float64 (GaussianDiffusion.ddim_coefficients; the
- * reverse step is the same call with the alphas_cumprod_next tables).  sigma == NULL selects the DETERMINISTIC rule
- * (eta = 0, reverse): noise / noise_in / noise_out / seed are then never read or written and may be NULL, and no random
- * numbers are generated.  With sigma != NULL the noise stream is lfvdm_p_sample_rng's: the same (seed, t, element) gives
- * the same z under either rule.  pred_xstart / eps_out / noise_out may be NULL; x and sample may alias. */
-int lfvdm_ddim_sample(const float* x, const float* eps, const float* noise, const int64_t* t, const float* sqrt_recip_acp,
-                      const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
-                      float* sample, float* pred_xstart, int B, int inner, void* stream);
-int lfvdm_ddim_sample_rng(const float* x, const float* eps, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
-                          const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
-                          float* sample, float* pred_xstart, int B, int inner, const int64_t* seed, void* stream);
-/* lfvdm_conv_out_psample with the DDIM rule (same shapes: lfvdm_conv_out_psample_ok). */
-int lfvdm_conv_out_ddim(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
-                        const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
-                        const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
-                        float* sample, float* pred_xstart, int B, int T, int H, int W, int C, int Cout, const int64_t* seed,
-                        void* stream);
-/* x0-prediction models (predict_xstart=True, ModelMeanType.START_X, gaussian_diffusion.py:305-326): what the network
- * returns is a second COMPILE-TIME property of the same three kernels.  The three entries below carry it next to the
- * rule and dispatch over the 3 rules x 2 mean types; the six entries above keep their signatures and their code.
- *   mean_type LFVDM_MEAN_X0:  p0 = clamp(model_out) - sqrt_recip_acp / sqrt_recipm1_acp are never read and may be NULL
- *   mean_type LFVDM_MEAN_EPS: p0 = clamp(sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] model_out), as above
- *   rule LFVDM_RULE_ANCESTRAL: c1 / c2 = posterior_mean_coef1 / 2, sg = the log-variance table (required)
- *   rule LFVDM_RULE_DDIM:      c1 / c2 = k1 / k2, sg = sigma, or NULL for the deterministic rule (no noise, no seed)
- * then sample = c1[t] p0 + c2[t] x + [t != 0] sigma z for either mean type, with the same noise stream (the same
- * (seed, t, element) gives the same z).  An unknown rule or mean_type -> LFVDM_E_SHAPE.  pred_xstart / mean_out /
- * noise_out / out (the convolution's result) may be NULL; x and sample may alias.  Shapes of the fused launch:
- * lfvdm_conv_out_psample_ok. */
+/* The reverse step x_t -> x_{t-1}: p_mean_variance + p_sample (:290-346,369-401) and ddim_sample / ddim_reverse_sample
+ * (:524-610), one formula per element of batch row b, t = t[b]:
+ *     p0     = clamp(x0-hat) to [-1, 1] if clip
+ *     mean   = c1[t] p0 + c2[t] x
+ *     sample = mean + [t != 0] sigma z
+ * over two independent choices, each a compile-time property of the kernels:
+ *   mean_type  LFVDM_MEAN_EPS  x0-hat = sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] model_out   (:341-346)
+ *              LFVDM_MEAN_X0   x0-hat = model_out (predict_xstart=True, :305-326); sqrt_recip_acp / sqrt_recipm1_acp are
+ *                              never read and may be NULL
+ *   rule       LFVDM_RULE_ANCESTRAL           c1 / c2 = posterior_mean_coef1 / 2, sg = the log-variance table (required),
+ *                                             sigma = exp(0.5 sg[t])
+ *              LFVDM_RULE_DDIM, sg != NULL    c1 / c2 = k1 / k2, sg = the sigma table, sigma = sg[t]; k1, k2, sigma are folded
+ *                                             on the host in float64 (GaussianDiffusion.ddim_coefficients; the reverse step
+ *                                             is the same call with the alphas_cumprod_next tables)
+ *              LFVDM_RULE_DDIM, sg == NULL    the DETERMINISTIC rule (eta = 0, reverse): sigma = 0, no random numbers are
+ *                                             generated, and noise / noise_in / noise_out / seed are never read or written
+ *                                             and may be NULL
+ * Three launches compute it:
+ *   lfvdm_update_x0           z = noise[b][i], required unless deterministic; not read where t[b] == 0.
+ *   lfvdm_update_rng_x0       z drawn in the kernel (one launch less than th.randn + lfvdm_update_x0): Philox4x32-10 keyed by
+ *                             seed[0] (device int64, one value per chain, required unless deterministic), counter = (element
+ *                             quad, batch row, t[b]) -> Box-Muller.  noise_out (optional) receives the z that were used.
+ *   lfvdm_conv_out_update_x0  the U-Net's 3x3 output convolution (unet.py:399-403,462-464) and the update in ONE launch:
+ *                             model_out = conv(act) + bias from the channels-last rows act [B*T*H*W][C] = SiLU(GN(h)) and the
+ *                             packed filters Wp [Cout][9][C] (lfvdm_pack_conv_weight); inner = T*Cout*H*W.  z = noise_in if
+ *                             given, else drawn from seed as in lfvdm_update_rng_x0 (one of the two required unless
+ *                             deterministic).  out (optional) receives model_out.  lfvdm_conv_out_psample_ok: 0 if the shape
+ *                             is covered (Cout 3 or 4, C 64 / 128 / 256, W % 4 == 0), else this entry returns
+ *                             LFVDM_E_UNSUPPORTED.
+ * Noise stream: the same (seed, t, element) gives the same z in every rule x mean_type cell, in the fused launch, and
+ * whatever the launch geometry.  x and sample may alias (the sampler updates its state in place).  pred_xstart (= p0),
+ * mean_out, noise_out and out may be NULL; every other pointer not named above is required.  An unknown rule or mean_type,
+ * a missing required pointer or a non-positive size -> LFVDM_E_SHAPE. */
 #define LFVDM_RULE_ANCESTRAL 0
 #define LFVDM_RULE_DDIM 1
 #define LFVDM_MEAN_EPS 0
@@ -591,6 +570,7 @@ int lfvdm_update_rng_x0(const float* x, const float* model_out, float* noise_out
                         const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg, int rule,
                         int mean_type, int clip, float* sample, float* pred_xstart, float* mean_out, int B, int inner,
                         const int64_t* seed, void* stream);
+int lfvdm_conv_out_psample_ok(int N, int H, int W, int C, int Cout);
 int lfvdm_conv_out_update_x0(const float* act, const float* Wp, const float* bias, float* out, const float* x,
                              const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
                              const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg, int rule,

@@ -19,8 +19,8 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
 }
 
-// The update rule of the three update kernels below, a COMPILE-TIME choice (the ancestral instantiations are the code they
-// were before the DDIM rules existed):
+// The x_{t-1} update (include/lfvdm_hip.h) is three kernels - given noise, noise drawn in the kernel, fused with the output
+// convolution - over two COMPILE-TIME choices.  The update rule:
 //   RULE_ANCESTRAL  mean = c1[t] p0 + c2[t] x, sigma = exp(0.5 logvar[t])                          (:369-401)
 //   RULE_DDIM       the same form with the folded DDIM coefficients k1[t], k2[t] in the c1 / c2 slots and sigma[t] itself
 //                   in the logvar slot (ddim_sample / ddim_reverse_sample, :524-610; folded on the host in float64, see
@@ -28,12 +28,11 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
 //   RULE_DDIM_DET   eta = 0 and the reverse step: no sigma table, no noise read, no Philox rounds, no noise store
 enum { RULE_ANCESTRAL = 0, RULE_DDIM = 1, RULE_DDIM_DET = 2 };
 
-// What the network's output IS, the second COMPILE-TIME choice of the same three kernels (ModelMeanType, :305-326):
+// What the network's output IS (ModelMeanType, :305-326):
 //   MEAN_EPS  the noise: p0 = sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] eps      (_predict_xstart_from_eps, :341-346)
 //   MEAN_X0   x0-hat itself (predict_xstart=True): p0 = the output; the two tables are neither loaded nor multiplied and
 //             their pointers may be null
-// Everything behind p0 - clamp, c1 p0 + c2 x, the noise (same key, counter and stream), the stores - is shared text.  The
-// MEAN_EPS instantiations are instruction for instruction the kernels they were before MEAN existed.
+// Everything behind p0 - clamp, c1 p0 + c2 x, the noise (same key, counter and stream), the stores - is shared text.
 enum { MEAN_EPS = 0, MEAN_X0 = 1 };
 
 template <int MEAN>
@@ -43,9 +42,29 @@ __device__ __forceinline__ float mean_x0hat(float r, float rm1, float xv, float 
 
 template <int RULE>
 __device__ __forceinline__ float rule_sigma(const float* __restrict__ t_logvar, int64_t tb) {
-    if (RULE == RULE_ANCESTRAL) return tb != 0 ? expf(0.5f * t_logvar[tb]) : 0.f;
+    if (RULE == RULE_ANCESTRAL) return tb != 0 ? expf(0.5f * t_logvar[tb]) : 0.f;      // [t != 0] exp(0.5 log_variance), :396-400
     if (RULE == RULE_DDIM) return tb != 0 ? t_logvar[tb] : 0.f;
     return 0.f;
+}
+
+// The coefficients of batch row b's step, gathered once per thread from the five tables at tb = t[b].  No __restrict__ on
+// the tables here: what the compiler may assume about them is what the calling kernel's own parameters say.
+struct StepCoef { float r, rm1, c1, c2, sigma; };
+
+template <int RULE, int MEAN>
+__device__ __forceinline__ StepCoef step_coef(int64_t tb, const float* t_recip, const float* t_recipm1, const float* t_c1,
+                                              const float* t_c2, const float* t_logvar) {
+    return {MEAN == MEAN_EPS ? t_recip[tb] : 0.f, MEAN == MEAN_EPS ? t_recipm1[tb] : 0.f, t_c1[tb], t_c2[tb],
+            rule_sigma<RULE>(t_logvar, tb)};
+}
+
+// p0 = the (clamped) x0-hat; returns the mean c1 p0 + c2 x (q_posterior_mean_variance, :228-231).  The noise is NOT applied
+// here: the given-noise kernel adds it only where t != 0 and must not read its buffer at t = 0, the other two always add.
+template <int MEAN>
+__device__ __forceinline__ float step_mean(const StepCoef& k, float xv, float out, int clip, float& p0) {
+    p0 = mean_x0hat<MEAN>(k.r, k.rm1, xv, out);
+    if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
+    return k.c1 * p0 + k.c2 * xv;
 }
 
 // x and sample may alias (the sampler updates its state in place): no __restrict__ on them.
@@ -59,18 +78,13 @@ __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const flo
                                                        float* __restrict__ mean_out, int inner) {
     const int b = blockIdx.y;
     const int64_t tb = t[b];
-    const float r = MEAN == MEAN_EPS ? t_recip[tb] : 0.f, rm1 = MEAN == MEAN_EPS ? t_recipm1[tb] : 0.f;
-    const float c1 = t_c1[tb], c2 = t_c2[tb];
-    // sample = mean + [t != 0] * exp(0.5 * log_variance) * noise     (:396-400)
-    const float sigma = rule_sigma<RULE>(t_logvar, tb);
+    const StepCoef k = step_coef<RULE, MEAN>(tb, t_recip, t_recipm1, t_c1, t_c2, t_logvar);
     const size_t base = (size_t)b * inner;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += gridDim.x * blockDim.x) {
-        const float xv = x[base + i];
-        float p0 = mean_x0hat<MEAN>(r, rm1, xv, eps[base + i]);
-        if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
-        const float mean = c1 * p0 + c2 * xv;       // q_posterior_mean_variance (:228-231)
+        float p0;
+        const float mean = step_mean<MEAN>(k, x[base + i], eps[base + i], clip, p0);
         float sv = mean;
-        if (RULE != RULE_DDIM_DET && tb != 0) sv += sigma * noise[base + i];
+        if (RULE != RULE_DDIM_DET && tb != 0) sv += k.sigma * noise[base + i];
         sample[base + i] = sv;
         if (pred) pred[base + i] = p0;
         if (mean_out) mean_out[base + i] = mean;
@@ -116,9 +130,7 @@ __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const
                                                            const int64_t* __restrict__ seed) {
     const int b = blockIdx.y;
     const int64_t tb = t[b];
-    const float r = MEAN == MEAN_EPS ? t_recip[tb] : 0.f, rm1 = MEAN == MEAN_EPS ? t_recipm1[tb] : 0.f;
-    const float c1 = t_c1[tb], c2 = t_c2[tb];
-    const float sigma = rule_sigma<RULE>(t_logvar, tb);
+    const StepCoef k = step_coef<RULE, MEAN>(tb, t_recip, t_recipm1, t_c1, t_c2, t_logvar);
     const unsigned long long key = RULE != RULE_DDIM_DET ? (unsigned long long)seed[0] : 0ull;
     const unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
     const size_t base = (size_t)b * inner;
@@ -130,11 +142,9 @@ __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const
         for (int e = 0; e < 4; ++e) {
             const int i = 4 * qd + e;
             if (i < inner) {
-                const float xv = x[base + i];
-                float p0 = mean_x0hat<MEAN>(r, rm1, xv, eps[base + i]);
-                if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
-                const float mean = c1 * p0 + c2 * xv;
-                sample[base + i] = RULE != RULE_DDIM_DET ? mean + sigma * z[e] : mean;
+                float p0;
+                const float mean = step_mean<MEAN>(k, x[base + i], eps[base + i], clip, p0);
+                sample[base + i] = RULE != RULE_DDIM_DET ? mean + k.sigma * z[e] : mean;
                 if (RULE != RULE_DDIM_DET && noise_out) noise_out[base + i] = z[e];
                 if (pred) pred[base + i] = p0;
                 if (mean_out) mean_out[base + i] = mean;
@@ -223,9 +233,7 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
     const int i = ((tt * CO + co) * p.H + y) * p.W + x;             // element of the (T, C, H, W) frame stack
     const size_t at = (size_t)b * inner + i;
     const int64_t tb = p.t[b];
-    const float r = MEAN == MEAN_EPS ? p.t_recip[tb] : 0.f, rm1 = MEAN == MEAN_EPS ? p.t_recipm1[tb] : 0.f;
-    const float c1 = p.t_c1[tb], c2 = p.t_c2[tb];
-    const float sigma = rule_sigma<RULE>(p.t_logvar, tb);
+    const StepCoef k = step_coef<RULE, MEAN>(tb, p.t_recip, p.t_recipm1, p.t_c1, p.t_c2, p.t_logvar);
     float z = 0.f;
     if (RULE == RULE_DDIM_DET) {
     } else if (p.noise_in) {
@@ -235,11 +243,9 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
         const f32x4 z4 = normal4((unsigned)(i >> 2), (unsigned)b, (unsigned)tb, (unsigned)key, (unsigned)(key >> 32));
         z = j == 0 ? z4.x : j == 1 ? z4.y : j == 2 ? z4.z : z4.w;  // x = 4 * xq + j and W % 4 == 0: i & 3 == j
     }
-    const float xv = p.x[at];
-    float p0 = mean_x0hat<MEAN>(r, rm1, xv, e);
-    if (p.clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
-    const float mean = c1 * p0 + c2 * xv;
-    p.sample[at] = RULE != RULE_DDIM_DET ? mean + sigma * z : mean;
+    float p0;
+    const float mean = step_mean<MEAN>(k, p.x[at], e, p.clip, p0);
+    p.sample[at] = RULE != RULE_DDIM_DET ? mean + k.sigma * z : mean;
     if (p.eps_out) p.eps_out[at] = e;
     if (RULE != RULE_DDIM_DET && p.noise_out) p.noise_out[at] = z;
     if (p.pred) p.pred[at] = p0;
@@ -375,12 +381,19 @@ extern "C" int lfvdm_sampler_tick(int64_t* t, const float* model_timestep_table,
     return LFVDM_OK;
 }
 
+extern "C" int lfvdm_conv_out_psample_ok(int N, int H, int W, int C, int Cout) {
+    if (N <= 0 || H <= 0 || W <= 0 || W % 4 || (Cout != 3 && Cout != 4)) return LFVDM_E_UNSUPPORTED;
+    if (C != 64 && C != 128 && C != 256) return LFVDM_E_UNSUPPORTED;
+    if ((long)N * H * W * C >= (1L << 31) / 4) return LFVDM_E_UNSUPPORTED;
+    return LFVDM_OK;
+}
+
+// ---- the three update entries: validate once (update_cell), then launch the cell's instantiation (on_grid)
 namespace {
-template <int RULE, int MEAN = MEAN_EPS>
+template <int RULE, int MEAN>
 int launch_update(const float* x, const float* eps, const float* noise, const int64_t* t, const float* recip, const float* recipm1,
                   const float* c1, const float* c2, const float* sg, int clip, float* sample, float* pred, float* mean_out, int B,
                   int inner, void* stream) {
-    if (B <= 0 || inner <= 0) return LFVDM_E_SHAPE;
     int gx = (inner + 255) / 256;
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL((p_sample_kernel<RULE, MEAN>), dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise, t, recip, recipm1, c1,
@@ -389,11 +402,10 @@ int launch_update(const float* x, const float* eps, const float* noise, const in
     return LFVDM_OK;
 }
 
-template <int RULE, int MEAN = MEAN_EPS>
+template <int RULE, int MEAN>
 int launch_update_rng(const float* x, const float* eps, float* noise_out, const int64_t* t, const float* recip,
                       const float* recipm1, const float* c1, const float* c2, const float* sg, int clip, float* sample, float* pred,
                       float* mean_out, int B, int inner, const int64_t* seed, void* stream) {
-    if (B <= 0 || inner <= 0 || (RULE != RULE_DDIM_DET && !seed)) return LFVDM_E_SHAPE;
     int gx = ((inner + 3) / 4 + 255) / 256;
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL((p_sample_rng_kernel<RULE, MEAN>), dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise_out, t, recip,
@@ -401,58 +413,8 @@ int launch_update_rng(const float* x, const float* eps, float* noise_out, const 
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
-}  // namespace
 
-extern "C" int lfvdm_p_sample(const float* x, const float* eps, const float* noise, const int64_t* t,
-                              const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* coef1,
-                              const float* coef2, const float* log_var, int clip, float* sample, float* pred_xstart,
-                              float* mean_out, int B, int inner, void* stream) {
-    return launch_update<RULE_ANCESTRAL>(x, eps, noise, t, sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, log_var, clip, sample,
-                                         pred_xstart, mean_out, B, inner, stream);
-}
-
-extern "C" int lfvdm_p_sample_rng(const float* x, const float* eps, float* noise_out, const int64_t* t,
-                                  const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* coef1,
-                                  const float* coef2, const float* log_var, int clip, float* sample, float* pred_xstart,
-                                  float* mean_out, int B, int inner, const int64_t* seed, void* stream) {
-    return launch_update_rng<RULE_ANCESTRAL>(x, eps, noise_out, t, sqrt_recip_acp, sqrt_recipm1_acp, coef1, coef2, log_var, clip,
-                                             sample, pred_xstart, mean_out, B, inner, seed, stream);
-}
-
-// DDIM: sigma == NULL selects the deterministic rule (eta = 0, and the reverse step): noise / seed are then never read
-extern "C" int lfvdm_ddim_sample(const float* x, const float* eps, const float* noise, const int64_t* t,
-                                 const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* k1, const float* k2,
-                                 const float* sigma, int clip, float* sample, float* pred_xstart, int B, int inner, void* stream) {
-    if (!x || !eps || !t || !sqrt_recip_acp || !sqrt_recipm1_acp || !k1 || !k2 || !sample) return LFVDM_E_SHAPE;
-    if (!sigma)
-        return launch_update<RULE_DDIM_DET>(x, eps, nullptr, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, nullptr, clip, sample,
-                                            pred_xstart, nullptr, B, inner, stream);
-    if (!noise) return LFVDM_E_SHAPE;
-    return launch_update<RULE_DDIM>(x, eps, noise, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, sigma, clip, sample, pred_xstart,
-                                    nullptr, B, inner, stream);
-}
-
-extern "C" int lfvdm_ddim_sample_rng(const float* x, const float* eps, float* noise_out, const int64_t* t,
-                                     const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* k1, const float* k2,
-                                     const float* sigma, int clip, float* sample, float* pred_xstart, int B, int inner,
-                                     const int64_t* seed, void* stream) {
-    if (!x || !eps || !t || !sqrt_recip_acp || !sqrt_recipm1_acp || !k1 || !k2 || !sample) return LFVDM_E_SHAPE;
-    if (!sigma)
-        return launch_update_rng<RULE_DDIM_DET>(x, eps, nullptr, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, nullptr, clip, sample,
-                                                pred_xstart, nullptr, B, inner, nullptr, stream);
-    return launch_update_rng<RULE_DDIM>(x, eps, noise_out, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, sigma, clip, sample,
-                                        pred_xstart, nullptr, B, inner, seed, stream);
-}
-
-extern "C" int lfvdm_conv_out_psample_ok(int N, int H, int W, int C, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || W % 4 || (Cout != 3 && Cout != 4)) return LFVDM_E_UNSUPPORTED;
-    if (C != 64 && C != 128 && C != 256) return LFVDM_E_UNSUPPORTED;
-    if ((long)N * H * W * C >= (1L << 31) / 4) return LFVDM_E_UNSUPPORTED;
-    return LFVDM_OK;
-}
-
-namespace {
-template <int RULE, int MEAN = MEAN_EPS>
+template <int RULE, int MEAN>
 int launch_head(const HeadUpdate& p, int Cout, void* stream) {
     if (int rc = lfvdm_conv_out_psample_ok(p.N, p.H, p.W, p.C, Cout)) return rc;
     const long quads = (long)p.N * p.H * (p.W / 4);
@@ -470,38 +432,8 @@ int launch_head(const HeadUpdate& p, int Cout, void* stream) {
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
-}  // namespace
 
-extern "C" int lfvdm_conv_out_psample(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
-                                      const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
-                                      const float* sqrt_recipm1_acp, const float* coef1, const float* coef2,
-                                      const float* log_var, int clip, float* sample, float* pred_xstart, float* mean_out,
-                                      int B, int T, int H, int W, int C, int Cout, const int64_t* seed, void* stream) {
-    if (B <= 0 || T <= 0 || !act || !Wp || !bias || !x || !sample || !t || (!noise_in && !seed)) return LFVDM_E_SHAPE;
-    const HeadUpdate p = {act, Wp, bias, x, noise_in, eps_out, noise_out, sample, pred_xstart, mean_out, t, seed, sqrt_recip_acp,
-                          sqrt_recipm1_acp, coef1, coef2, log_var, B * T, T, H, W, C, clip};
-    return launch_head<RULE_ANCESTRAL>(p, Cout, stream);
-}
-
-// the DDIM rules in the same launch; sigma == NULL: deterministic (noise_in / noise_out / seed are never touched)
-extern "C" int lfvdm_conv_out_ddim(const float* act, const float* Wp, const float* bias, float* eps_out, const float* x,
-                                   const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
-                                   const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* sigma, int clip,
-                                   float* sample, float* pred_xstart, int B, int T, int H, int W, int C, int Cout,
-                                   const int64_t* seed, void* stream) {
-    if (B <= 0 || T <= 0 || !act || !Wp || !bias || !x || !sample || !t || !sqrt_recip_acp || !sqrt_recipm1_acp || !k1 || !k2)
-        return LFVDM_E_SHAPE;
-    if (sigma && !noise_in && !seed) return LFVDM_E_SHAPE;
-    const HeadUpdate p = {act, Wp, bias, x, sigma ? noise_in : nullptr, eps_out, sigma ? noise_out : nullptr, sample, pred_xstart,
-                          nullptr, t, sigma ? seed : nullptr, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, sigma, B * T, T, H, W, C,
-                          clip};
-    return sigma ? launch_head<RULE_DDIM>(p, Cout, stream) : launch_head<RULE_DDIM_DET>(p, Cout, stream);
-}
-
-// ---- the entries that carry the mean type (include/lfvdm_hip.h: LFVDM_RULE_* / LFVDM_MEAN_*).  rule DDIM with
-// sigma == NULL is the deterministic instantiation, as in lfvdm_ddim_sample.  The six entries above stay what they are.
-namespace {
-// -> RULE_* of the template grid, or -1
+// -> RULE_* of the template grid, or -1: DDIM without a sigma table is the deterministic rule
 int grid_rule(int rule, const float* sg) {
     if (rule == LFVDM_RULE_ANCESTRAL) return sg ? RULE_ANCESTRAL : -1;
     if (rule == LFVDM_RULE_DDIM) return sg ? RULE_DDIM : RULE_DDIM_DET;
@@ -511,9 +443,17 @@ bool mean_ok(int mean_type, const float* recip, const float* recipm1) {
     if (mean_type == LFVDM_MEAN_X0) return true;
     return mean_type == LFVDM_MEAN_EPS && recip && recipm1;
 }
-}  // namespace
+// Everything the three entries check alike -> the cell's RULE_*, or -1.  have_noise: the entry's own source of z (a noise
+// buffer or a seed), required in every cell but the deterministic one.
+int update_cell(int rule, int mean_type, const float* x, const float* model_out, const int64_t* t, const float* recip,
+                const float* recipm1, const float* c1, const float* c2, const float* sg, const float* sample, int B, int inner,
+                bool have_noise) {
+    const int R = grid_rule(rule, sg);
+    if (R < 0 || !mean_ok(mean_type, recip, recipm1)) return -1;
+    if (B <= 0 || inner <= 0 || !x || !model_out || !t || !c1 || !c2 || !sample) return -1;
+    return R == RULE_DDIM_DET || have_noise ? R : -1;
+}
 
-namespace {
 template <int V> struct Const { static constexpr int value = V; };
 // f(Const<RULE>, Const<MEAN>) on the cell of the 3 x 2 template grid
 template <class F>
@@ -532,9 +472,9 @@ extern "C" int lfvdm_update_x0(const float* x, const float* model_out, const flo
                                const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* c1, const float* c2,
                                const float* sg, int rule, int mean_type, int clip, float* sample, float* pred_xstart,
                                float* mean_out, int B, int inner, void* stream) {
-    const int R = grid_rule(rule, sg);
-    if (R < 0 || !mean_ok(mean_type, sqrt_recip_acp, sqrt_recipm1_acp)) return LFVDM_E_SHAPE;
-    if (!x || !model_out || !t || !c1 || !c2 || !sample || (R != RULE_DDIM_DET && !noise)) return LFVDM_E_SHAPE;
+    const int R = update_cell(rule, mean_type, x, model_out, t, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, sample, B, inner,
+                              noise != nullptr);
+    if (R < 0) return LFVDM_E_SHAPE;
     return on_grid(R, mean_type, [&](auto r, auto m) {
         return launch_update<decltype(r)::value, decltype(m)::value>(
             x, model_out, decltype(r)::value == RULE_DDIM_DET ? nullptr : noise, t, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg,
@@ -546,9 +486,9 @@ extern "C" int lfvdm_update_rng_x0(const float* x, const float* model_out, float
                                    const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* c1, const float* c2,
                                    const float* sg, int rule, int mean_type, int clip, float* sample, float* pred_xstart,
                                    float* mean_out, int B, int inner, const int64_t* seed, void* stream) {
-    const int R = grid_rule(rule, sg);
-    if (R < 0 || !mean_ok(mean_type, sqrt_recip_acp, sqrt_recipm1_acp)) return LFVDM_E_SHAPE;
-    if (!x || !model_out || !t || !c1 || !c2 || !sample) return LFVDM_E_SHAPE;
+    const int R = update_cell(rule, mean_type, x, model_out, t, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, sample, B, inner,
+                              seed != nullptr);
+    if (R < 0) return LFVDM_E_SHAPE;
     return on_grid(R, mean_type, [&](auto r, auto m) {
         constexpr bool det = decltype(r)::value == RULE_DDIM_DET;
         return launch_update_rng<decltype(r)::value, decltype(m)::value>(
@@ -557,16 +497,16 @@ extern "C" int lfvdm_update_rng_x0(const float* x, const float* model_out, float
     });
 }
 
+// model_out of the fused launch is the convolution's result: act / Wp / bias stand in for it
 extern "C" int lfvdm_conv_out_update_x0(const float* act, const float* Wp, const float* bias, float* out, const float* x,
                                         const float* noise_in, float* noise_out, const int64_t* t, const float* sqrt_recip_acp,
                                         const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg,
                                         int rule, int mean_type, int clip, float* sample, float* pred_xstart, float* mean_out,
                                         int B, int T, int H, int W, int C, int Cout, const int64_t* seed, void* stream) {
-    const int R = grid_rule(rule, sg);
-    if (R < 0 || !mean_ok(mean_type, sqrt_recip_acp, sqrt_recipm1_acp)) return LFVDM_E_SHAPE;
-    if (B <= 0 || T <= 0 || !act || !Wp || !bias || !x || !sample || !t || !c1 || !c2) return LFVDM_E_SHAPE;
+    const int R = update_cell(rule, mean_type, x, act, t, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, sample, B, T,
+                              noise_in || seed);
+    if (R < 0 || !Wp || !bias) return LFVDM_E_SHAPE;
     const bool det = R == RULE_DDIM_DET;
-    if (!det && !noise_in && !seed) return LFVDM_E_SHAPE;
     const HeadUpdate p = {act, Wp, bias, x, det ? nullptr : noise_in, out, det ? nullptr : noise_out, sample, pred_xstart, mean_out,
                           t, det ? nullptr : seed, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, B * T, T, H, W, C, clip};
     return on_grid(R, mean_type, [&](auto r, auto m) { return launch_head<decltype(r)::value, decltype(m)::value>(p, Cout, stream); });

@@ -796,8 +796,7 @@ class Plan:
         covered (the sampler then issues the update as its own launch).  ``ddim``: the device tables k1 / k2 / sigma of
         ``GaussianDiffusion.ddim_tables`` - the DDIM rule (sigma None: deterministic, no noise buffer and no seed are handed
         to the kernel).  ``predict_xstart``: the network returns x0-hat (no sqrt_recip tables are handed over).  Every rule
-        and mean type goes through this one general entry (``update_args``); lfvdm_conv_out_psample and
-        lfvdm_conv_out_ddim launch the same kernels and remain exported for users of the C ABI."""
+        and mean type goes through this one entry (``update_args``)."""
         L = nat.lib()
         h = self.head
         if self.head_fused:

@@ -128,12 +128,7 @@ _SIGS = {
     "lfvdm_compose_rows": ([c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_conv_in_tick": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_i, c_fp, c_i,
                             c_fp], c_i),
-    "lfvdm_p_sample_rng": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp], c_i),
     "lfvdm_conv_out_psample_ok": ([c_i] * 5, c_i),
-    "lfvdm_conv_out_psample": ([c_fp] * 13 + [c_i, c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp], c_i),
-    "lfvdm_ddim_sample": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
-    "lfvdm_ddim_sample_rng": ([c_fp] * 9 + [c_i, c_fp, c_fp, c_i, c_i, c_fp, c_fp], c_i),
-    "lfvdm_conv_out_ddim": ([c_fp] * 13 + [c_i, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp], c_i),
     "lfvdm_update_x0": ([c_fp] * 9 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i, c_i, c_fp], c_i),
     "lfvdm_update_rng_x0": ([c_fp] * 9 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i, c_i, c_fp, c_fp], c_i),
     "lfvdm_conv_out_update_x0": ([c_fp] * 13 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i] * 6 + [c_fp, c_fp], c_i),
@@ -183,7 +178,6 @@ _SIGS = {
     "lfvdm_attn_temporal": ([c_fp] * 7 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_adamw_ema": ([C.POINTER(AdamWArgs), c_fp], c_i),
     "lfvdm_q_sample": ([c_fp] * 6 + [c_i, c_i, c_fp], c_i),
-    "lfvdm_p_sample": ([c_fp] * 9 + [c_i] + [c_fp] * 3 + [c_i, c_i, c_fp], c_i),
     "lfvdm_masked_mse": ([c_fp] * 4 + [c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_prepare_batch": ([c_fp] * 6 + [c_i] * 4 + [c_fp], c_i),
     "lfvdm_chain_plan": ([C.POINTER(ChainStage), c_i, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
@@ -646,65 +640,13 @@ def q_sample(x0, noise, t, sa, sb, out):
                                x0.numel() // B, stream()), "lfvdm_q_sample")
 
 
-def p_sample(x, eps, noise, t, recip, recipm1, c1, c2, logvar, clip, sample, pred=None, mean=None):
-    B = x.shape[0]
-    check(lib().lfvdm_p_sample(ptr(x), ptr(eps), ptr(noise), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1),
-                               ptr(c2), ptr(logvar), int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B,
-                               x.numel() // B, stream()), "lfvdm_p_sample")
-
-
-def p_sample_rng(x, eps, noise_out, t, recip, recipm1, c1, c2, logvar, clip, sample, seed, pred=None, mean=None):
-    """p_sample with the noise drawn in the kernel (Philox keyed by the device int64 ``seed``)."""
-    B = x.shape[0]
-    check(lib().lfvdm_p_sample_rng(ptr(x), ptr(eps), ptr(noise_out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1),
-                                   ptr(c2), ptr(logvar), int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B,
-                                   x.numel() // B, ptr(seed, torch.int64), stream()), "lfvdm_p_sample_rng")
-
-
-def conv_out_psample(act, wp, bias, eps_out, x, noise_in, noise_out, t, recip, recipm1, c1, c2, logvar, clip, sample, seed,
-                     pred=None, mean=None):
-    """The U-Net's output conv and the x_{t-1} update in one launch (lfvdm_conv_out_psample).  act: channels-last rows
-    [B*T*H*W][C]; wp: packed filters [Cout][9][C]; x / sample / eps_out: (B, T, Cout, H, W)."""
-    B, T, Cout, H, W = x.shape
-    check(lib().lfvdm_conv_out_psample(ptr(act), ptr(wp), ptr(bias), ptr(eps_out), ptr(x), ptr(noise_in), ptr(noise_out),
-                                       ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1), ptr(c2), ptr(logvar),
-                                       int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B, T, H, W, act.shape[-1], Cout,
-                                       ptr(seed, torch.int64) if seed is not None else None, stream()),
-          "lfvdm_conv_out_psample")
-
-
-def ddim_sample(x, eps, noise, t, recip, recipm1, k1, k2, sigma, clip, sample, pred=None):
-    """The DDIM update with given noise (lfvdm_ddim_sample); ``sigma=None``: the deterministic rule, ``noise`` is not read."""
-    B = x.shape[0]
-    check(lib().lfvdm_ddim_sample(ptr(x), ptr(eps), ptr(noise), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1), ptr(k2),
-                                  ptr(sigma), int(bool(clip)), ptr(sample), ptr(pred), B, x.numel() // B, stream()),
-          "lfvdm_ddim_sample")
-
-
-def ddim_sample_rng(x, eps, noise_out, t, recip, recipm1, k1, k2, sigma, clip, sample, seed, pred=None):
-    """The DDIM update with the noise drawn in the kernel (lfvdm_p_sample_rng's stream); ``sigma=None``: no noise at all."""
-    B = x.shape[0]
-    check(lib().lfvdm_ddim_sample_rng(ptr(x), ptr(eps), ptr(noise_out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1),
-                                      ptr(k2), ptr(sigma), int(bool(clip)), ptr(sample), ptr(pred), B, x.numel() // B,
-                                      ptr(seed, torch.int64) if seed is not None else None, stream()), "lfvdm_ddim_sample_rng")
-
-
-def conv_out_ddim(act, wp, bias, eps_out, x, noise_in, noise_out, t, recip, recipm1, k1, k2, sigma, clip, sample, seed, pred=None):
-    """The U-Net's output conv and the DDIM update in one launch (lfvdm_conv_out_ddim); layouts as conv_out_psample."""
-    B, T, Cout, H, W = x.shape
-    check(lib().lfvdm_conv_out_ddim(ptr(act), ptr(wp), ptr(bias), ptr(eps_out), ptr(x), ptr(noise_in), ptr(noise_out),
-                                    ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1), ptr(k2), ptr(sigma), int(bool(clip)),
-                                    ptr(sample), ptr(pred), B, T, H, W, act.shape[-1], Cout,
-                                    ptr(seed, torch.int64) if seed is not None else None, stream()), "lfvdm_conv_out_ddim")
-
-
 RULE_ANCESTRAL, RULE_DDIM = 0, 1      # LFVDM_RULE_* / LFVDM_MEAN_* of include/lfvdm_hip.h
 MEAN_EPS, MEAN_X0 = 0, 1
 
 
 def update_x0(x, out, noise, t, recip, recipm1, c1, c2, sg, rule, mean_type, clip, sample, pred=None, mean=None):
-    """The x_{t-1} update with given noise for either mean type (lfvdm_update_x0).  ``out``: the network's output;
-    MEAN_X0: ``recip`` / ``recipm1`` may be None; RULE_DDIM with ``sg=None``: deterministic, ``noise`` is not read."""
+    """The x_{t-1} update with given noise (lfvdm_update_x0).  ``out``: the network's output; MEAN_X0: ``recip`` /
+    ``recipm1`` may be None; RULE_DDIM with ``sg=None``: deterministic, ``noise`` is not read."""
     B = x.shape[0]
     check(lib().lfvdm_update_x0(ptr(x), ptr(out), ptr(noise), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1), ptr(c2),
                                 ptr(sg), int(rule), int(mean_type), int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B,
@@ -712,7 +654,8 @@ def update_x0(x, out, noise, t, recip, recipm1, c1, c2, sg, rule, mean_type, cli
 
 
 def update_rng_x0(x, out, noise_out, t, recip, recipm1, c1, c2, sg, rule, mean_type, clip, sample, seed, pred=None, mean=None):
-    """The same update with the noise drawn in the kernel (lfvdm_update_rng_x0; lfvdm_p_sample_rng's stream)."""
+    """The same update with the noise drawn in the kernel (lfvdm_update_rng_x0): Philox keyed by the device int64 ``seed``;
+    ``noise_out`` (optional) receives the values used."""
     B = x.shape[0]
     check(lib().lfvdm_update_rng_x0(ptr(x), ptr(out), ptr(noise_out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1),
                                     ptr(c2), ptr(sg), int(rule), int(mean_type), int(bool(clip)), ptr(sample), ptr(pred),
@@ -722,8 +665,9 @@ def update_rng_x0(x, out, noise_out, t, recip, recipm1, c1, c2, sg, rule, mean_t
 
 def conv_out_update_x0(act, wp, bias, out, x, noise_in, noise_out, t, recip, recipm1, c1, c2, sg, rule, mean_type, clip, sample,
                        seed, pred=None, mean=None):
-    """The U-Net's output conv and the update in one launch for either mean type (lfvdm_conv_out_update_x0); layouts as
-    conv_out_psample."""
+    """The U-Net's output conv and the update in one launch (lfvdm_conv_out_update_x0).  act: channels-last rows
+    [B*T*H*W][C]; wp: packed filters [Cout][9][C]; x / sample / out: (B, T, Cout, H, W); ``noise_in=None``: the noise is
+    update_rng_x0's for the same seed."""
     B, T, Cout, H, W = x.shape
     check(lib().lfvdm_conv_out_update_x0(ptr(act), ptr(wp), ptr(bias), ptr(out), ptr(x), ptr(noise_in), ptr(noise_out),
                                          ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1), ptr(c2), ptr(sg), int(rule),

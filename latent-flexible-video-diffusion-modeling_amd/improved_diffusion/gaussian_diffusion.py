@@ -16,11 +16,9 @@ What is native here
     noise, the replayed step, the fused head launch) is shared with epsilon prediction, and ``training_losses`` regresses
     on ``x_start``;
   * every update the package issues - eager (``_update``), replayed (``GraphSampler._step_body``) or fused into the output
-    convolution (``Plan.fuse_head_update``) - goes through the three general entries lfvdm_update_x0, lfvdm_update_rng_x0 and
-    lfvdm_conv_out_update_x0 with the arguments of ONE descriptor (``_update_args``: tables, rule, mean type).  The six older
-    entries (lfvdm_p_sample[_rng], lfvdm_ddim_sample[_rng], lfvdm_conv_out_psample, lfvdm_conv_out_ddim) launch the same
-    kernels and remain exported, bound and wrapped for users of the C ABI.
-
+    convolution (``Plan.fuse_head_update``) - goes through the library's three update entries lfvdm_update_x0,
+    lfvdm_update_rng_x0 and lfvdm_conv_out_update_x0 with the arguments of ONE descriptor (``_update_args``: tables, rule,
+    mean type);
   * the variational bound (``use_kl=True`` training, ``_vb_terms_bpd``, ``_prior_bpd``, ``calc_bpd_loop[_subsampled]``,
     reference :687-720, :743-753, :798-888, losses.py) with fixed sigma: the KL / discretized-decoder term of a batch row,
     its x0 and epsilon MSEs and its closed-form gradient are two HIP kernels (csrc/vb_terms.hip, ``_autograd._VbTerm``);

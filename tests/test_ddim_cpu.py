@@ -11,7 +11,7 @@ from conftest import GOLDEN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PIXEL = {"diffusion_space": "pixel", "pre_encoded": False, "pre_encoded_stats_dict": None}
-NEW_EXPORTS = ("lfvdm_ddim_sample", "lfvdm_ddim_sample_rng", "lfvdm_conv_out_ddim")
+NEW_EXPORTS = ("lfvdm_update_x0", "lfvdm_update_rng_x0", "lfvdm_conv_out_update_x0")      # DDIM is LFVDM_RULE_DDIM of these
 
 
 def make_diffusion(resp):
@@ -82,6 +82,8 @@ def test_new_exports_are_bound_and_declared():
     for name in NEW_EXPORTS:
         assert name in _native.EXPORTS, name
         assert name in declared, name
+    assert int(re.search(r"#define LFVDM_RULE_DDIM (\d+)", hdr).group(1)) == _native.RULE_DDIM
+    assert "sg == NULL" in hdr and "DETERMINISTIC" in hdr, "the header says how the deterministic rule is selected"
 
 
 def test_sampling_args_default_to_the_ancestral_chain():

@@ -56,18 +56,19 @@ def _run_kernel(kind, diff, x, eps, z, t, co, clip, seed=None):
     r, rm1 = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
     sample, pred = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
     if kind == "given":
-        nat.ddim_sample(x, eps, z, t, r, rm1, co["k1"], co["k2"], co["sigma"], clip, sample, pred)
+        nat.update_x0(x, eps, z, t, r, rm1, co["k1"], co["k2"], co["sigma"], nat.RULE_DDIM, nat.MEAN_EPS, clip, sample, pred)
         return sample, pred, z, None
     if kind == "rng":
         zo = torch.full_like(x, float("nan"))
-        nat.ddim_sample_rng(x, eps, zo, t, r, rm1, co["k1"], co["k2"], co["sigma"], clip, sample, seed, pred)
+        nat.update_rng_x0(x, eps, zo, t, r, rm1, co["k1"], co["k2"], co["sigma"], nat.RULE_DDIM, nat.MEAN_EPS, clip, sample, seed,
+                          pred)
         return sample, pred, zo, None
     act, wp, bias = _one_hot_head(eps)
     assert nat.lib().lfvdm_conv_out_psample_ok(x.shape[0] * x.shape[1], x.shape[3], x.shape[4], act.shape[1], x.shape[2]) == 0
     eps_out = torch.full_like(x, float("nan"))
     zo = torch.full_like(x, float("nan"))
-    nat.conv_out_ddim(act, wp, bias, eps_out, x, z if seed is None else None, zo if seed is not None else None, t, r, rm1,
-                      co["k1"], co["k2"], co["sigma"], clip, sample, seed, pred)
+    nat.conv_out_update_x0(act, wp, bias, eps_out, x, z if seed is None else None, zo if seed is not None else None, t, r, rm1,
+                           co["k1"], co["k2"], co["sigma"], nat.RULE_DDIM, nat.MEAN_EPS, clip, sample, seed, pred)
     return sample, pred, (zo if seed is not None else z), eps_out
 
 
@@ -141,12 +142,13 @@ def test_eta0_does_no_noise_work():
                 sample, pred = torch.full_like(x, 7.0), torch.full_like(x, 7.0)
                 zbuf = nan.clone()
                 if kind == "given":
-                    nat.ddim_sample(x, eps, zbuf, t, r, rm1, co["k1"], co["k2"], None, True, sample, pred)
+                    nat.update_x0(x, eps, zbuf, t, r, rm1, co["k1"], co["k2"], None, nat.RULE_DDIM, nat.MEAN_EPS, True, sample, pred)
                 elif kind == "rng":
-                    nat.ddim_sample_rng(x, eps, zbuf, t, r, rm1, co["k1"], co["k2"], None, True, sample, seed, pred)
-                else:
-                    nat.conv_out_ddim(act, wp, bias, None, x, zbuf, zbuf, t, r, rm1, co["k1"], co["k2"], None, True, sample,
+                    nat.update_rng_x0(x, eps, zbuf, t, r, rm1, co["k1"], co["k2"], None, nat.RULE_DDIM, nat.MEAN_EPS, True, sample,
                                       seed, pred)
+                else:
+                    nat.conv_out_update_x0(act, wp, bias, None, x, zbuf, zbuf, t, r, rm1, co["k1"], co["k2"], None,
+                                           nat.RULE_DDIM, nat.MEAN_EPS, True, sample, seed, pred)
                 torch.cuda.synchronize()
                 assert torch.isfinite(sample).all() and torch.isfinite(pred).all(), kind
                 assert torch.isnan(zbuf).all(), f"{kind}: the noise buffer is neither read nor written"
@@ -156,8 +158,8 @@ def test_eta0_does_no_noise_work():
 
 
 def test_eta_positive_draws_the_ancestral_noise_stream():
-    """Same (seed, t, element) -> the same z under either rule: what lfvdm_ddim_sample_rng and lfvdm_conv_out_ddim write
-    to noise_out is bitwise what lfvdm_p_sample_rng writes."""
+    """Same (seed, t, element) -> the same z under either rule: what lfvdm_update_rng_x0 and lfvdm_conv_out_update_x0 write
+    to noise_out under LFVDM_RULE_DDIM is bitwise what lfvdm_update_rng_x0 writes under LFVDM_RULE_ANCESTRAL."""
     from improved_diffusion import _native as nat
     g = np.load(os.path.join(GOLDEN, "ddim_update.npz"))
     diff = make_diffusion("ddim50")
@@ -170,9 +172,10 @@ def test_eta_positive_draws_the_ancestral_noise_stream():
     for seed_value in (5, -77):
         seed = torch.tensor([seed_value], dtype=torch.int64, device="cuda")
         z_anc, z_ddim = torch.zeros_like(x), torch.zeros_like(x)
-        nat.p_sample_rng(x, eps, z_anc, t, r, rm1, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
-                         tb["model_log_variance"], True, torch.empty_like(x), seed)
-        nat.ddim_sample_rng(x, eps, z_ddim, t, r, rm1, co["k1"], co["k2"], co["sigma"], True, torch.empty_like(x), seed)
+        nat.update_rng_x0(x, eps, z_anc, t, r, rm1, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
+                          tb["model_log_variance"], nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, torch.empty_like(x), seed)
+        nat.update_rng_x0(x, eps, z_ddim, t, r, rm1, co["k1"], co["k2"], co["sigma"], nat.RULE_DDIM, nat.MEAN_EPS, True,
+                          torch.empty_like(x), seed)
         _, _, z_fused, _ = _run_kernel("fused", diff, x, eps, None, t, co, True, seed)
         torch.cuda.synchronize()
         assert float(z_anc.std()) > 0.5

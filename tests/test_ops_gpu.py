@@ -561,9 +561,9 @@ def test_diffusion_ops(nat):
     nat.q_sample(x0.cuda(), noise.cuda(), t.cuda(), dev(tab.sqrt_alphas_cumprod), dev(tab.sqrt_one_minus_alphas_cumprod), out)
     close(out, do.q_sample(tab, x0, t, noise), 1e-6)
     smp, pred, mean = (torch.empty_like(out) for _ in range(3))
-    nat.p_sample(x.cuda(), eps.cuda(), noise.cuda(), t.cuda(), dev(tab.sqrt_recip_alphas_cumprod),
-                 dev(tab.sqrt_recipm1_alphas_cumprod), dev(tab.posterior_mean_coef1), dev(tab.posterior_mean_coef2),
-                 dev(tab.fixed_large_log_variance), True, smp, pred, mean)
+    nat.update_x0(x.cuda(), eps.cuda(), noise.cuda(), t.cuda(), dev(tab.sqrt_recip_alphas_cumprod),
+                  dev(tab.sqrt_recipm1_alphas_cumprod), dev(tab.posterior_mean_coef1), dev(tab.posterior_mean_coef2),
+                  dev(tab.fixed_large_log_variance), nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, smp, pred, mean)
     ref_s, ref_p = do.p_sample(tab, eps, x, t, noise)
     close(smp, ref_s, 1e-5)
     close(pred, ref_p, 1e-4)  # 157x amplification at t=999 before the clamp
@@ -850,7 +850,7 @@ def test_gn_temporal_backward(nat, B, T, P, C, accumulate):
 
 
 def test_p_sample_rng_draws_standard_normal_noise(nat):
-    """lfvdm_p_sample_rng: the update of lfvdm_p_sample with the noise drawn in the kernel (Philox4x32-10 + Box-Muller,
+    """lfvdm_update_rng_x0: the update of lfvdm_update_x0 with the noise drawn in the kernel (Philox4x32-10 + Box-Muller,
     keyed by a per-chain seed, counter = (element, batch row, timestep)).  The values it reports are the ones it used, they
     are standard normal, a (seed, t, element) triple is reproducible, other timesteps / seeds / rows are independent, t = 0
     adds no noise (gaussian_diffusion.py:396-400)."""
@@ -863,12 +863,12 @@ def test_p_sample_rng_draws_standard_normal_noise(nat):
     def run(t, sd, want_noise=True):
         tt = torch.tensor(t, dtype=torch.int64, device="cuda")
         out, nz = torch.empty(B, inner, device="cuda"), torch.empty(B, inner, device="cuda") if want_noise else None
-        nat.p_sample_rng(x, eps, nz, tt, *tabs, True, out, sd, None, None)
+        nat.update_rng_x0(x, eps, nz, tt, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, out, sd, None, None)
         return out, nz, tt
 
     out, nz, tt = run([7, 7, 500, 0], seed)
     ref = torch.empty_like(out)
-    nat.p_sample(x, eps, nz, tt, *tabs, True, ref)                        # the plain kernel on the reported noise
+    nat.update_x0(x, eps, nz, tt, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, ref)      # the given-noise kernel on the reported noise
     assert torch.equal(out, ref)
     z = nz[:3].flatten().double().cpu().numpy()                            # (row 3 is t = 0: its noise is not used)
     assert abs(z.mean()) < 4e-3 and abs(z.var() - 1) < 6e-3 and abs(stats.kurtosis(z)) < 0.03 and abs(stats.skew(z)) < 0.01
@@ -883,14 +883,14 @@ def test_p_sample_rng_draws_standard_normal_noise(nat):
     out0, _, _ = run([7, 7, 500, 0], seed, want_noise=False)
     assert torch.equal(out0, out)                                          # the noise output is optional
     mean = torch.empty_like(out)
-    nat.p_sample(x, eps, torch.zeros_like(x), tt, *tabs, True, torch.empty_like(out), None, mean)
+    nat.update_x0(x, eps, torch.zeros_like(x), tt, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, torch.empty_like(out), None, mean)
     assert torch.equal(out[3], mean[3])                                    # t = 0: the sample is the posterior mean
 
 
 @pytest.mark.parametrize("B,T,H,W,C,Cout", [(2, 20, 16, 16, 64, 4), (1, 3, 8, 12, 128, 3), (2, 2, 4, 4, 256, 4)])
 def test_conv_out_psample_equals_conv_then_update(nat, B, T, H, W, C, Cout):
-    """lfvdm_conv_out_psample = the output convolution (unet.py:402,462-464) + lfvdm_p_sample_rng in one launch: its eps
-    equals the dense convolution, its noise is the SAME stream as lfvdm_p_sample_rng's for the chain's seed (bitwise), and
+    """lfvdm_conv_out_update_x0 = the output convolution (unet.py:402,462-464) + lfvdm_update_rng_x0 in one launch: its eps
+    equals the dense convolution, its noise is the SAME stream as lfvdm_update_rng_x0's for the chain's seed (bitwise), and
     its sample / pred_xstart are bitwise what the two-launch form gives on that eps; with injected noise it uses that noise."""
     N = B * T
     a = rnd("co/a", N, C, H, W)
@@ -903,19 +903,20 @@ def test_conv_out_psample_equals_conv_then_update(nat, B, T, H, W, C, Cout):
     seed = torch.tensor([0x7654321], dtype=torch.int64, device="cuda")
     act, wp = cl(a), packed(nat, w)
     eps, nz, out, pred = (torch.empty_like(x) for _ in range(4))
-    nat.conv_out_psample(act, wp, bias.cuda(), eps, x, None, nz, t, *tabs, True, out, seed, pred)
+    nat.conv_out_update_x0(act, wp, bias.cuda(), eps, x, None, nz, t, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, out, seed, pred)
     err = float((eps.cpu() - ref_eps).abs().max())
     assert err < 5e-5, err
     out2, nz2, pred2 = (torch.empty_like(x) for _ in range(3))
-    nat.p_sample_rng(x.view(B, -1), eps.view(B, -1), nz2.view(B, -1), t, *tabs, True, out2.view(B, -1), seed, pred2.view(B, -1))
+    nat.update_rng_x0(x.view(B, -1), eps.view(B, -1), nz2.view(B, -1), t, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, out2.view(B, -1), seed,
+                      pred2.view(B, -1))
     assert torch.equal(nz, nz2) and torch.equal(out, out2) and torch.equal(pred, pred2)
     given = rnd("co/n", B, T, Cout, H, W).cuda()
     out3, out4 = torch.empty_like(x), torch.empty_like(x)
-    nat.conv_out_psample(act, wp, bias.cuda(), None, x, given, None, t, *tabs, True, out3, None)
-    nat.p_sample(x.view(B, -1), eps.view(B, -1), given.view(B, -1), t, *tabs, True, out4.view(B, -1))
+    nat.conv_out_update_x0(act, wp, bias.cuda(), None, x, given, None, t, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, out3, None)
+    nat.update_x0(x.view(B, -1), eps.view(B, -1), given.view(B, -1), t, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, out4.view(B, -1))
     assert torch.equal(out3, out4)
     xin = x.clone()                                     # in place, as the sampler runs it
-    nat.conv_out_psample(act, wp, bias.cuda(), None, xin, None, None, t, *tabs, True, xin, seed)
+    nat.conv_out_update_x0(act, wp, bias.cuda(), None, xin, None, None, t, *tabs, nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, xin, seed)
     assert torch.equal(xin, out)
 
 

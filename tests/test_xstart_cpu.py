@@ -12,8 +12,9 @@ from conftest import GOLDEN
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PIXEL = {"diffusion_space": "pixel", "pre_encoded": False, "pre_encoded_stats_dict": None}
 NEW_EXPORTS = ("lfvdm_update_x0", "lfvdm_update_rng_x0", "lfvdm_conv_out_update_x0")
-KEPT_EXPORTS = ("lfvdm_p_sample", "lfvdm_p_sample_rng", "lfvdm_ddim_sample", "lfvdm_ddim_sample_rng", "lfvdm_conv_out_psample",
-                "lfvdm_conv_out_ddim", "lfvdm_conv_out_psample_ok")
+KEPT_EXPORTS = ("lfvdm_conv_out_psample_ok",)
+RETIRED_EXPORTS = ("lfvdm_p_sample", "lfvdm_p_sample_rng", "lfvdm_ddim_sample", "lfvdm_ddim_sample_rng", "lfvdm_conv_out_psample",
+                   "lfvdm_conv_out_ddim")
 
 
 def make_diffusion(resp="", **kw):
@@ -55,11 +56,27 @@ def test_new_exports_are_bound_and_declared():
     for name in ("LFVDM_RULE_ANCESTRAL", "LFVDM_RULE_DDIM", "LFVDM_MEAN_EPS", "LFVDM_MEAN_X0"):
         value = int(re.search(rf"#define {name} (\d+)", hdr).group(1))
         assert getattr(_native, name[len("LFVDM_"):]) == value, name
-    # the general entries carry two ints (rule, mean type) more than lfvdm_p_sample[_rng] / lfvdm_conv_out_psample
-    for new, old in zip(NEW_EXPORTS, ("lfvdm_p_sample", "lfvdm_p_sample_rng", "lfvdm_conv_out_psample")):
-        assert len(_native._SIGS[new][0]) == len(_native._SIGS[old][0]) + 2, new
+    for name, nargs in zip(NEW_EXPORTS, (18, 19, 27)):
+        assert len(_native._SIGS[name][0]) == nargs, name
     for fn in ("update_x0", "update_rng_x0", "conv_out_update_x0"):
         assert callable(getattr(_native, fn))
+
+
+def test_retired_update_entries_are_gone():
+    """One update entry per launch kind: the six entries that each hand-picked one rule x mean type cell are neither
+    declared, bound, wrapped nor exported by the built library."""
+    import ctypes
+    from improved_diffusion import _native
+    hdr = open(os.path.join(ROOT, "include", "lfvdm_hip.h")).read()
+    declared = set(re.findall(r"\b(lfvdm_[a-z0-9_]+)\s*\(", hdr))
+    assert os.path.exists(_native.LIB_PATH), "run `python __graft_entry__.py` (build) first"
+    lib = ctypes.CDLL(_native.LIB_PATH)
+    assert all(hasattr(lib, name) for name in NEW_EXPORTS + KEPT_EXPORTS)
+    for name in RETIRED_EXPORTS:
+        assert name not in declared, name
+        assert name not in _native._SIGS and name not in _native.EXPORTS, name
+        assert not hasattr(_native, name[len("lfvdm_"):]), name
+        assert not hasattr(lib, name), name
 
 
 def test_public_signatures_are_unchanged():

@@ -215,21 +215,24 @@ def test_unknown_rule_or_mean_type_is_refused():
 
 
 def test_noise_stream_is_the_epsilon_mode_stream():
-    """Equal (seed, t, shape): noise_out of the x0 entries is bitwise what lfvdm_p_sample_rng writes; and the general
-    entries called with MEAN_EPS give bitwise the results of the entries they generalise."""
+    """Equal (seed, t, shape): noise_out of the x0 entries is bitwise what the MEAN_EPS ancestral lfvdm_update_rng_x0 writes;
+    and in every rule x mean type cell the given-noise entry, fed the noise the RNG entry reported, reproduces that entry's
+    sample and x0-hat bitwise (t holds 0 - where the noise is not applied - and nonzero steps)."""
     from improved_diffusion import _native as nat
     g = np.load(os.path.join(GOLDEN, "xstart_update.npz"))
     diff = make_diffusion("ddim50")
     case = "ddim50/t0"
     x, out = (torch.from_numpy(g[f"{case}/{k}"]).cuda() for k in ("x", "out"))
-    t = torch.from_numpy(g[f"{case}/t"]).cuda()
+    tv = g[f"{case}/t"]
+    assert (tv == 0).any() and (tv != 0).any()
+    t = torch.from_numpy(tv).cuda()
     tb = diff.tables("cuda")
     r, rm1 = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
     for seed_value in (5, -77):
         seed = torch.tensor([seed_value], dtype=torch.int64, device="cuda")
         z_eps, s_eps, p_eps = torch.zeros_like(x), torch.empty_like(x), torch.empty_like(x)
-        nat.p_sample_rng(x, out, z_eps, t, r, rm1, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
-                         tb["model_log_variance"], True, s_eps, seed, p_eps)
+        nat.update_rng_x0(x, out, z_eps, t, r, rm1, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"],
+                          tb["model_log_variance"], nat.RULE_ANCESTRAL, nat.MEAN_EPS, True, s_eps, seed, p_eps)
         assert float(z_eps.std()) > 0.5
         for mode in ("p", 0.5, 1.0):
             tabs = _tables(diff, mode)
@@ -237,11 +240,15 @@ def test_noise_stream_is_the_epsilon_mode_stream():
             _, _, _, z_fused, _ = _run_x0("fused", x, out, None, t, tabs, True, seed)
             torch.cuda.synchronize()
             assert torch.equal(z_rng, z_eps) and torch.equal(z_fused, z_eps), mode
-        c1, c2, sg, rule = _tables(diff, "p")
-        z2, s2, p2 = torch.zeros_like(x), torch.empty_like(x), torch.empty_like(x)
-        nat.update_rng_x0(x, out, z2, t, r, rm1, c1, c2, sg, rule, nat.MEAN_EPS, True, s2, seed, p2)
-        torch.cuda.synchronize()
-        assert torch.equal(z2, z_eps) and torch.equal(s2, s_eps) and torch.equal(p2, p_eps)
+        for mode in ("p", 1.0):
+            c1, c2, sg, rule = _tables(diff, mode)
+            for mean_type, rr, rr1 in ((nat.MEAN_EPS, r, rm1), (nat.MEAN_X0, None, None)):
+                z1, s1, p1, s2, p2 = (torch.full_like(x, float("nan")) for _ in range(5))
+                nat.update_rng_x0(x, out, z1, t, rr, rr1, c1, c2, sg, rule, mean_type, True, s1, seed, p1)
+                nat.update_x0(x, out, z1, t, rr, rr1, c1, c2, sg, rule, mean_type, True, s2, p2)
+                torch.cuda.synchronize()
+                assert torch.isfinite(s1).all() and torch.isfinite(p1).all(), (mode, mean_type)
+                assert torch.equal(z1, z_eps) and torch.equal(s2, s1) and torch.equal(p2, p1), (mode, mean_type)
 
 
 # ------------------------------------------------------------------------------------------------ trajectories
