@@ -576,6 +576,30 @@ int lfvdm_conv_out_update_x0(const float* act, const float* Wp, const float* bia
                              const float* sqrt_recipm1_acp, const float* c1, const float* c2, const float* sg, int rule,
                              int mean_type, int clip, float* sample, float* pred_xstart, float* mean_out, int B, int T, int H,
                              int W, int C, int Cout, const int64_t* seed, void* stream);
+/* The multistep rule: DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2, data-prediction form), a second-order update at one
+ * network evaluation per step.  Per element of batch row b, t = t[b]:
+ *     p0     = clamp(x0-hat) to [-1, 1] if clip                       (x0-hat by mean_type, as above)
+ *     sample = k1[t] p0 + k2[t] x                                     (the deterministic DDIM step = the first-order solver)
+ *     if k3[t] != 0:  sample += k3[t] (p0 - hist)                     (hist = the p0 of the step before, t + 1)
+ * k1 / k2 are the eta = 0 tables of LFVDM_RULE_DDIM and k3 is folded with them on the host in float64
+ * (GaussianDiffusion.dpm_solver_coefficients: 0 at the first step of a chain, which has no history, and at its last two).
+ * There is no noise, no random number and no seed.  A row whose k3[t[b]] is 0 never reads hist and its result is bitwise
+ * that of lfvdm_update_x0 under the deterministic LFVDM_RULE_DDIM; the two launches below agree bitwise with each other
+ * (given a convolution that reproduces model_out).
+ *   lfvdm_update_ms_x0           the stand-alone launch (inner elements per row).
+ *   lfvdm_conv_out_update_ms_x0  the update in the launch of the U-Net's output convolution: act / Wp / bias / out / the
+ *                                shapes and LFVDM_E_UNSUPPORTED as for lfvdm_conv_out_update_x0.
+ * hist may equal pred_xstart (the sampler keeps ONE buffer: each thread reads its element of hist before it writes that
+ * element of pred_xstart); x may equal sample.  hist == NULL: first order for every row (k3 is not read).  LFVDM_MEAN_EPS
+ * requires sqrt_recip_acp and sqrt_recipm1_acp, LFVDM_MEAN_X0 never reads them.  pred_xstart and out may be NULL; an unknown
+ * mean_type, a missing required pointer (k3 included) or a non-positive size -> LFVDM_E_SHAPE. */
+int lfvdm_update_ms_x0(const float* x, const float* model_out, const float* hist, const int64_t* t, const float* sqrt_recip_acp,
+                       const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* k3, int mean_type, int clip,
+                       float* sample, float* pred_xstart, int B, int inner, void* stream);
+int lfvdm_conv_out_update_ms_x0(const float* act, const float* Wp, const float* bias, float* out, const float* x,
+                                const float* hist, const int64_t* t, const float* sqrt_recip_acp, const float* sqrt_recipm1_acp,
+                                const float* k1, const float* k2, const float* k3, int mean_type, int clip, float* sample,
+                                float* pred_xstart, int B, int T, int H, int W, int C, int Cout, void* stream);
 /* Sampler clock of the captured denoising step (the loop `for i in indices: t = th.tensor([i]*B)` of
  * gaussian_diffusion.py:509-512 and _WrappedModel's timestep map, respace.py:117-122, kept on the device):
  * t[b] <- max(t[b] - 1, 0);  model_t[b] <- model_timestep_table[t[b]]. */

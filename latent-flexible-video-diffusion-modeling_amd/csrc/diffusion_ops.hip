@@ -26,7 +26,13 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
 //                   in the logvar slot (ddim_sample / ddim_reverse_sample, :524-610; folded on the host in float64, see
 //                   GaussianDiffusion.ddim_coefficients)
 //   RULE_DDIM_DET   eta = 0 and the reverse step: no sigma table, no noise read, no Philox rounds, no noise store
-enum { RULE_ANCESTRAL = 0, RULE_DDIM = 1, RULE_DDIM_DET = 2 };
+//   RULE_DPMPP2M    DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2): the deterministic DDIM mean of k1[t], k2[t], then
+//                   mean += k3[t] (p0 - hist) where k3[t] != 0; hist = the x0-hat of the step before.  No noise either
+//                   (multistep_mean below).
+//                   Only the given-noise kernel and the fused one are instantiated with it (lfvdm_update_ms_x0,
+//                   lfvdm_conv_out_update_ms_x0; GaussianDiffusion.dpm_solver_coefficients folds k3 in float64)
+enum { RULE_ANCESTRAL = 0, RULE_DDIM = 1, RULE_DDIM_DET = 2, RULE_DPMPP2M = 3 };
+constexpr bool rule_draws(int rule) { return rule == RULE_ANCESTRAL || rule == RULE_DDIM; }
 
 // What the network's output IS (ModelMeanType, :305-326):
 //   MEAN_EPS  the noise: p0 = sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] eps      (_predict_xstart_from_eps, :341-346)
@@ -67,6 +73,29 @@ __device__ __forceinline__ float step_mean(const StepCoef& k, float xv, float ou
     return k.c1 * p0 + k.c2 * xv;
 }
 
+// RULE_DPMPP2M: step_mean with its roundings SPELLED OUT, then the second-order term.  step_mean leaves the compiler free
+// to fuse either product of c1 p0 + c2 x (and of r x - rm1 out) into an fma, and it decides per instantiation: written
+// with step_mean, the multistep cells came out as packed multiplies plus an add, one rounding away from the deterministic
+// DDIM cells.  The intrinsics below are what p_sample_kernel<RULE_DDIM_DET> compiles to - p0 = fma(r, x, -(rm1 out)),
+// mean = fma(c2, x, c1 p0) - in BOTH multistep kernels, so a row whose k3 is 0 (the first step of a chain and the last two)
+// has the bits of lfvdm_update_x0's deterministic DDIM rule and never reads hist, and the fused launch has the bits of the
+// stand-alone one.  (conv_out_psample_kernel<.., RULE_DDIM_DET, MEAN_X0> happens to fuse the OTHER product, c1 p0: against
+// that one cell a k3 = 0 row can differ in the last bit.)  tests/test_dpm_solver_gpu.py holds all of this.
+template <int MEAN>
+__device__ __forceinline__ float multistep_mean(const StepCoef& k, float k3, float xv, float out, int clip, const float* hist,
+                                                size_t at, float& p0) {
+    p0 = MEAN == MEAN_X0 ? out : __fmaf_rn(k.r, xv, -__fmul_rn(k.rm1, out));
+    if (clip) p0 = fminf(fmaxf(p0, -1.f), 1.f);
+    float mean = __fmaf_rn(k.c2, xv, __fmul_rn(k.c1, p0));
+    if (k3 != 0.f) mean = __fmaf_rn(k3, __fsub_rn(p0, hist[at]), mean);
+    return mean;
+}
+
+// pred is written through a __restrict__ pointer except under RULE_DPMPP2M, whose hist may BE pred (each thread reads its
+// element of hist before it writes that element of pred)
+template <int RULE> struct PredOut { typedef float* __restrict__ ptr; };
+template <> struct PredOut<RULE_DPMPP2M> { typedef float* ptr; };
+
 // x and sample may alias (the sampler updates its state in place): no __restrict__ on them.
 template <int RULE, int MEAN>
 __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const float* __restrict__ eps,
@@ -74,17 +103,20 @@ __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const flo
                                                        const float* __restrict__ t_recip, const float* __restrict__ t_recipm1,
                                                        const float* __restrict__ t_c1, const float* __restrict__ t_c2,
                                                        const float* __restrict__ t_logvar, int clip,
-                                                       float* sample, float* __restrict__ pred,
-                                                       float* __restrict__ mean_out, int inner) {
+                                                       float* sample, typename PredOut<RULE>::ptr pred,
+                                                       float* __restrict__ mean_out, int inner, const float* hist,
+                                                       const float* __restrict__ t_k3) {
     const int b = blockIdx.y;
     const int64_t tb = t[b];
     const StepCoef k = step_coef<RULE, MEAN>(tb, t_recip, t_recipm1, t_c1, t_c2, t_logvar);
+    const float k3 = RULE == RULE_DPMPP2M ? t_k3[tb] : 0.f;
     const size_t base = (size_t)b * inner;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += gridDim.x * blockDim.x) {
         float p0;
-        const float mean = step_mean<MEAN>(k, x[base + i], eps[base + i], clip, p0);
+        const float mean = RULE == RULE_DPMPP2M ? multistep_mean<MEAN>(k, k3, x[base + i], eps[base + i], clip, hist, base + i, p0)
+                                                : step_mean<MEAN>(k, x[base + i], eps[base + i], clip, p0);
         float sv = mean;
-        if (RULE != RULE_DDIM_DET && tb != 0) sv += k.sigma * noise[base + i];
+        if (rule_draws(RULE) && tb != 0) sv += k.sigma * noise[base + i];
         sample[base + i] = sv;
         if (pred) pred[base + i] = p0;
         if (mean_out) mean_out[base + i] = mean;
@@ -167,6 +199,7 @@ struct HeadUpdate {
     const int64_t *t, *seed;
     const float *t_recip, *t_recipm1, *t_c1, *t_c2, *t_logvar;
     int N, T, H, W, C, clip;
+    const float *hist, *t_k3;      // RULE_DPMPP2M only
 };
 
 template <int CO, int CPL, int RULE, int MEAN>
@@ -235,7 +268,7 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
     const int64_t tb = p.t[b];
     const StepCoef k = step_coef<RULE, MEAN>(tb, p.t_recip, p.t_recipm1, p.t_c1, p.t_c2, p.t_logvar);
     float z = 0.f;
-    if (RULE == RULE_DDIM_DET) {
+    if (!rule_draws(RULE)) {
     } else if (p.noise_in) {
         z = p.noise_in[at];
     } else {
@@ -244,10 +277,11 @@ __global__ __launch_bounds__(256) void conv_out_psample_kernel(const HeadUpdate 
         z = j == 0 ? z4.x : j == 1 ? z4.y : j == 2 ? z4.z : z4.w;  // x = 4 * xq + j and W % 4 == 0: i & 3 == j
     }
     float p0;
-    const float mean = step_mean<MEAN>(k, p.x[at], e, p.clip, p0);
-    p.sample[at] = RULE != RULE_DDIM_DET ? mean + k.sigma * z : mean;
+    const float mean = RULE == RULE_DPMPP2M ? multistep_mean<MEAN>(k, p.t_k3[tb], p.x[at], e, p.clip, p.hist, at, p0)
+                                            : step_mean<MEAN>(k, p.x[at], e, p.clip, p0);
+    p.sample[at] = rule_draws(RULE) ? mean + k.sigma * z : mean;
     if (p.eps_out) p.eps_out[at] = e;
-    if (RULE != RULE_DDIM_DET && p.noise_out) p.noise_out[at] = z;
+    if (rule_draws(RULE) && p.noise_out) p.noise_out[at] = z;
     if (p.pred) p.pred[at] = p0;
     if (p.mean_out) p.mean_out[at] = mean;
 }
@@ -393,11 +427,11 @@ namespace {
 template <int RULE, int MEAN>
 int launch_update(const float* x, const float* eps, const float* noise, const int64_t* t, const float* recip, const float* recipm1,
                   const float* c1, const float* c2, const float* sg, int clip, float* sample, float* pred, float* mean_out, int B,
-                  int inner, void* stream) {
+                  int inner, void* stream, const float* hist = nullptr, const float* k3 = nullptr) {
     int gx = (inner + 255) / 256;
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL((p_sample_kernel<RULE, MEAN>), dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, eps, noise, t, recip, recipm1, c1,
-                       c2, sg, clip, sample, pred, mean_out, inner);
+                       c2, sg, clip, sample, pred, mean_out, inner, hist, k3);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
@@ -508,8 +542,51 @@ extern "C" int lfvdm_conv_out_update_x0(const float* act, const float* Wp, const
     if (R < 0 || !Wp || !bias) return LFVDM_E_SHAPE;
     const bool det = R == RULE_DDIM_DET;
     const HeadUpdate p = {act, Wp, bias, x, det ? nullptr : noise_in, out, det ? nullptr : noise_out, sample, pred_xstart, mean_out,
-                          t, det ? nullptr : seed, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, B * T, T, H, W, C, clip};
+                          t, det ? nullptr : seed, sqrt_recip_acp, sqrt_recipm1_acp, c1, c2, sg, B * T, T, H, W, C, clip,
+                          nullptr, nullptr};
     return on_grid(R, mean_type, [&](auto r, auto m) { return launch_head<decltype(r)::value, decltype(m)::value>(p, Cout, stream); });
+}
+
+// ---- the multistep entries: one rule (RULE_DPMPP2M; without a history, the deterministic DDIM cell itself), two mean types
+namespace {
+bool multistep_ok(int mean_type, const float* x, const float* model_out, const int64_t* t, const float* recip,
+                  const float* recipm1, const float* k1, const float* k2, const float* k3, const float* sample, int B, int inner) {
+    if (!mean_ok(mean_type, recip, recipm1)) return false;
+    return B > 0 && inner > 0 && x && model_out && t && k1 && k2 && k3 && sample;
+}
+// f(Const<RULE>, Const<MEAN>) on RULE_DPMPP2M, or on RULE_DDIM_DET where there is no history
+template <class F>
+int on_multistep(bool have_hist, int mean_type, F f) {
+    const bool x0 = mean_type == LFVDM_MEAN_X0;
+    if (have_hist) return x0 ? f(Const<RULE_DPMPP2M>(), Const<MEAN_X0>()) : f(Const<RULE_DPMPP2M>(), Const<MEAN_EPS>());
+    return x0 ? f(Const<RULE_DDIM_DET>(), Const<MEAN_X0>()) : f(Const<RULE_DDIM_DET>(), Const<MEAN_EPS>());
+}
+}  // namespace
+
+extern "C" int lfvdm_update_ms_x0(const float* x, const float* model_out, const float* hist, const int64_t* t,
+                                  const float* sqrt_recip_acp, const float* sqrt_recipm1_acp, const float* k1, const float* k2,
+                                  const float* k3, int mean_type, int clip, float* sample, float* pred_xstart, int B, int inner,
+                                  void* stream) {
+    if (!multistep_ok(mean_type, x, model_out, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, k3, sample, B, inner))
+        return LFVDM_E_SHAPE;
+    return on_multistep(hist != nullptr, mean_type, [&](auto r, auto m) {
+        return launch_update<decltype(r)::value, decltype(m)::value>(x, model_out, nullptr, t, sqrt_recip_acp, sqrt_recipm1_acp, k1,
+                                                                     k2, nullptr, clip, sample, pred_xstart, nullptr, B, inner,
+                                                                     stream, hist, k3);
+    });
+}
+
+extern "C" int lfvdm_conv_out_update_ms_x0(const float* act, const float* Wp, const float* bias, float* out, const float* x,
+                                           const float* hist, const int64_t* t, const float* sqrt_recip_acp,
+                                           const float* sqrt_recipm1_acp, const float* k1, const float* k2, const float* k3,
+                                           int mean_type, int clip, float* sample, float* pred_xstart, int B, int T, int H, int W,
+                                           int C, int Cout, void* stream) {
+    if (!multistep_ok(mean_type, x, act, t, sqrt_recip_acp, sqrt_recipm1_acp, k1, k2, k3, sample, B, T) || !Wp || !bias)
+        return LFVDM_E_SHAPE;
+    const HeadUpdate p = {act, Wp, bias, x, nullptr, out, nullptr, sample, pred_xstart, nullptr, t, nullptr, sqrt_recip_acp,
+                          sqrt_recipm1_acp, k1, k2, nullptr, B * T, T, H, W, C, clip, hist, k3};
+    return on_multistep(hist != nullptr, mean_type,
+                        [&](auto r, auto m) { return launch_head<decltype(r)::value, decltype(m)::value>(p, Cout, stream); });
 }
 
 extern "C" int lfvdm_masked_mse(const float* a, const float* b, const float* mask, float* out, int B, int T,

@@ -35,8 +35,13 @@ def update_args(tables, ddim=None, predict_xstart=False):
     lfvdm_update_rng_x0, lfvdm_conv_out_update_x0) take, from the device tables of ``GaussianDiffusion.tables`` and, for
     the DDIM rule, of ``GaussianDiffusion.ddim_tables``.  Ancestral: the posterior coefficients and the model's log
     variance; DDIM: the folded k1 / k2 / sigma (sigma None: the deterministic instantiation).  An x0-prediction model
-    hands no sqrt_recip tables over.  The only place that knows this mapping."""
-    if ddim is not None:
+    hands no sqrt_recip tables over.  The rule ("dpmpp2m",): ``ddim`` is ``GaussianDiffusion.dpm_solver_tables`` (k1 / k2 /
+    k3); the tuple then carries k3 in the ``sg`` place and RULE_DPMPP2M, and its update is launched through the multistep
+    entries (lfvdm_update_ms_x0, lfvdm_conv_out_update_ms_x0), which take no noise and no seed.  The only place that knows
+    this mapping."""
+    if ddim is not None and "k3" in ddim:
+        c1, c2, sg, rule = ddim["k1"], ddim["k2"], ddim["k3"], nat.RULE_DPMPP2M
+    elif ddim is not None:
         c1, c2, sg, rule = ddim["k1"], ddim["k2"], ddim["sigma"], nat.RULE_DDIM
     else:
         c1, c2, sg = tables["posterior_mean_coef1"], tables["posterior_mean_coef2"], tables["model_log_variance"]
@@ -795,8 +800,9 @@ class Plan:
         with the chain's in-kernel noise (or ``noise`` as given when ``inject_noise``).  -> False if the shape is not
         covered (the sampler then issues the update as its own launch).  ``ddim``: the device tables k1 / k2 / sigma of
         ``GaussianDiffusion.ddim_tables`` - the DDIM rule (sigma None: deterministic, no noise buffer and no seed are handed
-        to the kernel).  ``predict_xstart``: the network returns x0-hat (no sqrt_recip tables are handed over).  Every rule
-        and mean type goes through this one entry (``update_args``)."""
+        to the kernel), or k1 / k2 / k3 of ``dpm_solver_tables`` - the rule ("dpmpp2m",): lfvdm_conv_out_update_ms_x0 with
+        ``pred`` as the history it reads AND the x0-hat it writes.  ``predict_xstart``: the network returns x0-hat (no
+        sqrt_recip tables are handed over).  Every rule and mean type goes through this one entry (``update_args``)."""
         L = nat.lib()
         h = self.head
         if self.head_fused:
@@ -806,6 +812,13 @@ class Plan:
         self.keep.append((t_buf, tables, seed, noise, pred, ddim))
         recip, recipm1, c1, c2, sg, rule, mean_type = update_args(tables, ddim, predict_xstart)
         det, x0 = sg is None, recip is None
+        if rule == nat.RULE_DPMPP2M:
+            args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in), _p(pred), _p(t_buf),
+                    None if x0 else _p(recip), None if x0 else _p(recipm1), _p(c1), _p(c2), _p(sg), mean_type, int(bool(clip)),
+                    _p(self.x_in), _p(pred), self.B, self.T, self.H, self.W, h["C"], h["Cout"])
+            self.steps[h["step"]] = (L.lfvdm_conv_out_update_ms_x0, args)
+            self.head_fused = True
+            return True
         args = (_p(h["act"]), _p(h["Wp"]), _p(h["bias"]), _p(self.out), _p(self.x_in),
                 _p(noise) if inject_noise and not det else None, None if inject_noise or det else _p(noise), _p(t_buf),
                 None if x0 else _p(recip), None if x0 else _p(recipm1), _p(c1), _p(c2), None if det else _p(sg), rule, mean_type,

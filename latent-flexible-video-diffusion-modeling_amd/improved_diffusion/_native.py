@@ -132,6 +132,8 @@ _SIGS = {
     "lfvdm_update_x0": ([c_fp] * 9 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i, c_i, c_fp], c_i),
     "lfvdm_update_rng_x0": ([c_fp] * 9 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i, c_i, c_fp, c_fp], c_i),
     "lfvdm_conv_out_update_x0": ([c_fp] * 13 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i] * 6 + [c_fp, c_fp], c_i),
+    "lfvdm_update_ms_x0": ([c_fp] * 9 + [c_i, c_i] + [c_fp] * 2 + [c_i, c_i, c_fp], c_i),
+    "lfvdm_conv_out_update_ms_x0": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 2 + [c_i] * 6 + [c_fp], c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_vb_terms": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 4 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_vb_terms_bwd": ([c_fp] * 11 + [c_i, c_i, c_fp, c_i, c_i, c_i, c_fp], c_i),
@@ -642,6 +644,9 @@ def q_sample(x0, noise, t, sa, sb, out):
 
 RULE_ANCESTRAL, RULE_DDIM = 0, 1      # LFVDM_RULE_* / LFVDM_MEAN_* of include/lfvdm_hip.h
 MEAN_EPS, MEAN_X0 = 0, 1
+# not a value of the library's ``rule`` argument: the multistep rule has entries of its own (lfvdm_update_ms_x0,
+# lfvdm_conv_out_update_ms_x0).  _engine.update_args hands it out so that the callers can tell which entry to launch
+RULE_DPMPP2M = "dpmpp2m"
 
 
 def update_x0(x, out, noise, t, recip, recipm1, c1, c2, sg, rule, mean_type, clip, sample, pred=None, mean=None):
@@ -674,6 +679,26 @@ def conv_out_update_x0(act, wp, bias, out, x, noise_in, noise_out, t, recip, rec
                                          int(mean_type), int(bool(clip)), ptr(sample), ptr(pred), ptr(mean), B, T, H, W,
                                          act.shape[-1], Cout, ptr(seed, torch.int64) if seed is not None else None, stream()),
           "lfvdm_conv_out_update_x0")
+
+
+def update_ms_x0(x, out, hist, t, recip, recipm1, k1, k2, k3, mean_type, clip, sample, pred=None):
+    """The DPM-Solver++(2M) update (lfvdm_update_ms_x0): the deterministic DDIM step of ``k1`` / ``k2`` plus
+    ``k3[t] (x0-hat - hist)`` where ``k3[t] != 0``.  ``hist``: the x0-hat of the step before - it may BE ``pred`` - or None
+    for a first-order step in every row."""
+    B = x.shape[0]
+    check(lib().lfvdm_update_ms_x0(ptr(x), ptr(out), ptr(hist), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(k1), ptr(k2),
+                                   ptr(k3), int(mean_type), int(bool(clip)), ptr(sample), ptr(pred), B, x.numel() // B, stream()),
+          "lfvdm_update_ms_x0")
+
+
+def conv_out_update_ms_x0(act, wp, bias, out, x, hist, t, recip, recipm1, k1, k2, k3, mean_type, clip, sample, pred=None):
+    """The U-Net's output conv and the DPM-Solver++(2M) update in one launch (lfvdm_conv_out_update_ms_x0); act / wp / x /
+    sample / out as for ``conv_out_update_x0``, ``hist`` as for ``update_ms_x0``."""
+    B, T, Cout, H, W = x.shape
+    check(lib().lfvdm_conv_out_update_ms_x0(ptr(act), ptr(wp), ptr(bias), ptr(out), ptr(x), ptr(hist), ptr(t, torch.int64),
+                                            ptr(recip), ptr(recipm1), ptr(k1), ptr(k2), ptr(k3), int(mean_type), int(bool(clip)),
+                                            ptr(sample), ptr(pred), B, T, H, W, act.shape[-1], Cout, stream()),
+          "lfvdm_conv_out_update_ms_x0")
 
 
 def vb_terms(x_start, x_t, out, noise, t, recip, recipm1, c1, c2, post_logvar, model_logvar, mask, mean_type, clip, vb,

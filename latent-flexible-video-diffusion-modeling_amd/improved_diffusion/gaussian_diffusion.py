@@ -10,6 +10,12 @@ What is native here
   * DDIM (``ddim_sample``, ``ddim_reverse_sample``, ``ddim_sample_loop[_progressive]``, reference :524-685) is a second
     update rule of the same kernels and of the same replayed step; its per-timestep coefficients are folded on the host in
     float64 (``ddim_coefficients``);
+  * DPM-Solver++(2M) (``dpm_solver_sample``, ``dpm_solver_sample_loop[_progressive]``; Lu et al. 2022, Algorithm 2 - not in
+    the reference) is a third, second-order multistep rule of the same step: the deterministic DDIM mean plus
+    ``k3[t] (x0-hat - previous x0-hat)`` (``dpm_solver_coefficients``), one network evaluation and at most one update launch
+    per step (lfvdm_update_ms_x0, lfvdm_conv_out_update_ms_x0), the sampler's ``pred_xstart`` buffer as its only history.
+    Its accuracy claim rests on an analytic Gaussian model (tests/test_dpm_solver_cpu.py): sample
+    quality on a trained video model has not been measured;
   * x0-prediction models (``predict_xstart=True``, ``ModelMeanType.START_X``, reference :305-326, :779-788) are the second
     mean type of the same kernels, chosen at compile time next to the rule: x0-hat is the clamped network output, the
     ``sqrt_recip`` / ``sqrt_recipm1`` tables are not read, everything behind x0-hat (posterior mean or folded DDIM rule,
@@ -17,8 +23,8 @@ What is native here
     on ``x_start``;
   * every update the package issues - eager (``_update``), replayed (``GraphSampler._step_body``) or fused into the output
     convolution (``Plan.fuse_head_update``) - goes through the library's three update entries lfvdm_update_x0,
-    lfvdm_update_rng_x0 and lfvdm_conv_out_update_x0 with the arguments of ONE descriptor (``_update_args``: tables, rule,
-    mean type);
+    lfvdm_update_rng_x0 and lfvdm_conv_out_update_x0 (the multistep rule: their noise-free siblings lfvdm_update_ms_x0 and
+    lfvdm_conv_out_update_ms_x0) with the arguments of ONE descriptor (``_update_args``: tables, rule, mean type);
   * the variational bound (``use_kl=True`` training, ``_vb_terms_bpd``, ``_prior_bpd``, ``calc_bpd_loop[_subsampled]``,
     reference :687-720, :743-753, :798-888, losses.py) with fixed sigma: the KL / discretized-decoder term of a batch row,
     its x0 and epsilon MSEs and its closed-form gradient are two HIP kernels (csrc/vb_terms.hip, ``_autograd._VbTerm``);
@@ -196,6 +202,43 @@ class GaussianDiffusion:
             self._ddim_cache[key] = tb
         return tb
 
+    def dpm_solver_coefficients(self):
+        """float64 per-timestep tables {"k1", "k2", "k3"} of DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2, data-prediction
+        form) in the folded form the kernels evaluate:  sample = k1[t] p0 + k2[t] x + k3[t] (p0 - p0_prev).
+
+        With alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = log(alpha / sigma) and h = lambda_{t-1} - lambda_t, the
+        first-order step sigma_{t-1}/sigma_t x - alpha_{t-1} expm1(-h) p0 is exactly DDIM at eta = 0: k1 and k2 ARE the
+        arrays of ``ddim_coefficients(0.0)``.  The second-order step puts D = (1 + 1/(2r)) p0 - 1/(2r) p0_prev in p0's
+        place, r = (lambda_t - lambda_{t+1}) / h, which adds k3 = k1 / (2r) = k1 h / (2 (lambda_t - lambda_{t+1})).
+        k3 is 0 at t = n-1 (no history yet), at t = 0 (lambda_{-1} is infinite: the last sample is pred_xstart, as for
+        DDIM) and, on purpose, at t = 1: with uniform-in-t respacing the step onto original timestep 0 has r of about
+        0.2, and extrapolating over it loses to DDIM on the analytic model of DESIGN.md section 4."""
+        co = self._ddim_cache.get("dpmpp2m")
+        if co is None:
+            d = self.ddim_coefficients(0.0)
+            abar = self.alphas_cumprod
+            lam = 0.5 * (np.log(abar) - np.log1p(-abar))
+            n = self.num_timesteps
+            k3 = np.zeros(n, dtype=np.float64)
+            if n >= 4:
+                t = np.arange(2, n - 1)
+                k3[t] = d["k1"][t] * (lam[t - 1] - lam[t]) / (2.0 * (lam[t] - lam[t + 1]))
+            co = {"k1": d["k1"], "k2": d["k2"], "k3": k3}
+            self._ddim_cache["dpmpp2m"] = co
+        return co
+
+    def dpm_solver_tables(self, device):
+        """fp32 device copies of ``dpm_solver_coefficients``, uploaded once per device (k1 / k2: the tensors of
+        ``ddim_tables(device, 0.0)``)."""
+        key = ("dpmpp2m", str(device))
+        tb = self._ddim_cache.get(key)
+        if tb is None:
+            dd = self.ddim_tables(device, 0.0)
+            tb = {"k1": dd["k1"], "k2": dd["k2"],
+                  "k3": th.from_numpy(self.dpm_solver_coefficients()["k3"]).float().to(device)}
+            self._ddim_cache[key] = tb
+        return tb
+
     def _gather(self, name, t, ndim):
         return _bshape(self.tables(t.device)[name][t], ndim)
 
@@ -264,36 +307,51 @@ class GaussianDiffusion:
 
     # ------------------------------------------------------------------ p(x_{t-1} | x_t)
     def _update_args(self, device, rule=("ancestral",), reverse=False):
-        """(recip, recipm1, c1, c2, sg, RULE_*, MEAN_*) of the update ``rule`` - ("ancestral",) or ("ddim", eta) - of this
-        model's mean type: what every update launch of the package is issued with (``_engine.update_args``)."""
+        """(recip, recipm1, c1, c2, sg, RULE_*, MEAN_*) of the update ``rule`` - ("ancestral",), ("ddim", eta) or
+        ("dpmpp2m",), whose k3 rides in the ``sg`` place - of this model's mean type: what every update launch of the
+        package is issued with (``_engine.update_args``)."""
         from ._engine import update_args
-        ddim = self.ddim_tables(device, rule[1], reverse) if rule[0] == "ddim" else None
+        if rule[0] == "dpmpp2m":
+            ddim = self.dpm_solver_tables(device)
+        else:
+            ddim = self.ddim_tables(device, rule[1], reverse) if rule[0] == "ddim" else None
         return update_args(self.tables(device), ddim, self.predicts_xstart)
 
     # ``out`` below is the network's output: the noise, or x0-hat when ``predicts_xstart``
-    def _update(self, x, out, t, noise, clip_denoised, rule=("ancestral",), reverse=False, want_mean=False):
+    def _update(self, x, out, t, noise, clip_denoised, rule=("ancestral",), reverse=False, want_mean=False, hist=None):
         """One fused launch (lfvdm_update_x0) -> sample, x0-hat, and the mean on request.  ``noise`` None: the noise-free
         call of ``p_mean_variance`` (the ancestral kernel wants a pointer: ``x`` stands in); a deterministic DDIM rule
-        reads no noise at all."""
+        reads no noise at all.  The multistep rule (lfvdm_update_ms_x0) reads ``hist``, the x0-hat of the step before
+        (None: a first-order step), and no noise either."""
         recip, recipm1, c1, c2, sg, R, M = self._update_args(x.device, rule, reverse)
         sample = th.empty_like(x, memory_format=th.contiguous_format)
         pred = th.empty_like(sample)
+        if R == nat.RULE_DPMPP2M:
+            nat.update_ms_x0(x.contiguous(), out.contiguous(), None if hist is None else hist.contiguous(),
+                             t.to(th.int64).contiguous(), recip, recipm1, c1, c2, sg, M, clip_denoised, sample, pred)
+            return sample, pred, None
         mean = th.empty_like(sample) if want_mean else None
         z = None if sg is None else (noise if noise is not None else x).contiguous()
         nat.update_x0(x.contiguous(), out.contiguous(), z, t.to(th.int64).contiguous(), recip, recipm1, c1, c2, sg, R, M,
                       clip_denoised, sample, pred, mean)
         return sample, pred, mean
 
-    def _update_denoised(self, x, out, t, noise, clip_denoised, denoised_fn, rule=("ancestral",), reverse=False):
+    def _update_denoised(self, x, out, t, noise, clip_denoised, denoised_fn, rule=("ancestral",), reverse=False, hist=None):
         """The same update with a user function applied to x0-hat before clipping (reference process_xstart,
         :305-309).  ``denoised_fn`` is arbitrary Python on a tensor, so this rarely used variant is composed of
-        elementwise device ops around it instead of the fused kernel:  c1[t] * p0 + c2[t] * x + [t != 0] * sigma[t] * z."""
+        elementwise device ops around it instead of the fused kernel:  c1[t] * p0 + c2[t] * x + [t != 0] * sigma[t] * z,
+        or, under the multistep rule, + k3[t] * (p0 - hist) in the noise's place."""
         n = x.dim()
         pred = denoised_fn(self._xstart_from_output(x, t, out))
         if clip_denoised:
             pred = pred.clamp(-1, 1)
         _, _, c1, c2, sg, R, _ = self._update_args(x.device, rule, reverse)
         mean = _bshape(c1[t], n) * pred + _bshape(c2[t], n) * x
+        if R == nat.RULE_DPMPP2M:      # sg holds k3; rows with k3 = 0 (and a chain's first step: no hist) stay first order
+            if hist is not None:
+                k3 = _bshape(sg[t], n)
+                mean = th.where(k3 != 0, mean + k3 * (pred - hist), mean)
+            return mean, pred, mean
         if sg is None or noise is None:
             return mean, pred, mean
         sigma = th.exp(0.5 * sg[t]) if R == nat.RULE_ANCESTRAL else sg[t]      # the ancestral table holds log variances
@@ -381,8 +439,8 @@ class GaussianDiffusion:
 
     def _sample_loop(self, rule, model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress,
                      return_attn_weights=False, _reuse_buffers=False, _final_only=False):
-        """The chain of either rule - ("ancestral",) or ("ddim", eta) - behind both progressive loops; the dicts of the
-        ancestral chain carry ``attn`` as those of ``p_sample`` do."""
+        """The chain of any rule - ("ancestral",), ("ddim", eta) or ("dpmpp2m",) - behind the progressive loops; the dicts
+        of the ancestral chain carry ``attn`` as those of ``p_sample`` do."""
         from .unet import UNetVideoModel
         keys = ("sample", "pred_xstart", "attn") if rule[0] == "ancestral" else ("sample", "pred_xstart")
         if device is None:
@@ -422,12 +480,17 @@ class GaussianDiffusion:
                                            "launch per stage - run the chain again")
                 yield {k: (out[k] if _reuse_buffers or out[k] is None else out[k].clone()) for k in keys}
             return
+        prev = None      # the multistep rule's history: the x0-hat of the step before
         for i in indices:
             t = th.full((shape[0],), i, device=device, dtype=th.long)
             with th.no_grad():
                 if rule[0] == "ancestral":
                     out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                         model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
+                elif rule[0] == "dpmpp2m":
+                    out = self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                 model_kwargs=model_kwargs, prev_pred_xstart=prev)
+                    prev = out["pred_xstart"]
                 else:
                     out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                            model_kwargs=model_kwargs, eta=rule[1])
@@ -482,6 +545,42 @@ class GaussianDiffusion:
         ``GraphSampler`` under the conditions of ``p_sample_loop_progressive``."""
         return self._sample_loop(("ddim", float(eta)), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
                                  progress)
+
+    # ------------------------------------------------------------------ DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2)
+    def dpm_solver_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, prev_pred_xstart=None):
+        """x_{t-1} from the model by one DPM-Solver++(2M) step; same usage as ``ddim_sample`` at eta = 0, plus the history:
+        the caller threads the ``pred_xstart`` of the step before (t + 1) through as ``prev_pred_xstart``.  None - the first
+        step of a chain - gives the first-order step, which is the DDIM step."""
+        self._check_native_modes()
+        model_kwargs = model_kwargs or {}
+        assert t.shape == (x.shape[0],)
+        out, _ = model(x, self._scale_timesteps(t), return_attn_weights=False, **model_kwargs)
+        if denoised_fn is not None:
+            sample, pred, _ = self._update_denoised(x, out, t, None, clip_denoised, denoised_fn, ("dpmpp2m",),
+                                                    hist=prev_pred_xstart)
+        else:
+            sample, pred, _ = self._update(x, out, t, None, clip_denoised, ("dpmpp2m",), hist=prev_pred_xstart)
+        return {"sample": sample, "pred_xstart": pred}
+
+    def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                               device=None, progress=False, latent_mask=None, return_decoded=True):
+        """Full DPM-Solver++(2M) chain -> the final sample tensor alone; arguments and treatment of the final sample as
+        ``ddim_sample_loop``'s, without ``eta`` (the rule is deterministic)."""
+        if return_decoded and not self.can_decode():
+            raise NotImplementedError("dpm_solver_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); "
+                                      "pass return_decoded=False for latents - refused BEFORE the chain runs")
+        final = None
+        for sample in self._sample_loop(("dpmpp2m",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
+                                        progress, _reuse_buffers=True, _final_only=True):
+            final = sample
+        out = final["sample"].clone()
+        return self.decode(out) if return_decoded else out
+
+    def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                           model_kwargs=None, device=None, progress=False):
+        """Generator over the dicts of ``dpm_solver_sample`` for t = T-1 .. 0; replayed through ``GraphSampler`` under the
+        conditions of ``p_sample_loop_progressive``."""
+        return self._sample_loop(("dpmpp2m",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress)
 
     def _graph_sampler(self, unet, shape, clip_denoised, rule=("ancestral",)):
         # the update rule is part of the key (appended: position 1 stays the shape): a DDIM chain and an ancestral chain on
@@ -882,16 +981,23 @@ class GraphSampler(ReplayedStep):
     captured as a hipGraph over the engine's static buffers; ``step`` is a single replay."""
 
     def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False, rule=("ancestral",)):
-        # rule: ("ancestral",) or ("ddim", eta) - which update closes the step; fixed for the life of the captured graphs
+        # rule: ("ancestral",), ("ddim", eta) or ("dpmpp2m",) - which update closes the step; fixed for the life of the
+        # captured graphs
         self.rule = tuple(rule)
-        if self.rule[0] not in ("ancestral", "ddim") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
+        if self.rule[0] not in ("ancestral", "ddim", "dpmpp2m") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
             raise ValueError(f"unknown update rule {rule!r}")
         super().__init__(diffusion, unet, shape, clip_denoised, inject_noise)
         dev = self.plan.dev
-        # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic), and what the update is launched with
-        self.ddim = diffusion.ddim_tables(dev, self.rule[1]) if self.rule[0] == "ddim" else None
+        # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic) or k1 / k2 / k3 of the multistep rule,
+        # and what the update is launched with
+        self.multistep = self.rule[0] == "dpmpp2m"
+        if self.multistep:
+            self.ddim = diffusion.dpm_solver_tables(dev)
+        else:
+            self.ddim = diffusion.ddim_tables(dev, self.rule[1]) if self.rule[0] == "ddim" else None
         self.update = diffusion._update_args(dev, self.rule)
         self.noise = th.empty(self.shape, device=dev)
+        # the step's x0-hat; under the multistep rule also the history the next step reads (in and out of one launch)
         self.pred = th.empty(self.shape, device=dev)
         # the replayed step draws its noise inside the update kernel (lfvdm_update_rng_x0: Philox keyed by a per-chain seed
         # that begin() takes from torch's generator, so th.manual_seed still fixes the video); LFVDM_SAMPLER_NOISE=torch
@@ -910,7 +1016,8 @@ class GraphSampler(ReplayedStep):
         import os
         pl = self.plan
         recip, recipm1, c1, c2, sg, rule, mean_type = self.update
-        det = sg is None        # DDIM with eta = 0: no noise of any kind, whatever the noise settings say
+        # DDIM with eta = 0 and the multistep rule (sg is its k3): no noise of any kind, whatever the noise settings say
+        det = sg is None or self.multistep
         in_kernel = det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
         # the x_{t-1} update rides in the plan's last launch (output conv + update: lfvdm_conv_out_update_x0) where the
         # shape allows; LFVDM_FUSED_HEAD=0 keeps the two launches (A/B aid)
@@ -930,6 +1037,10 @@ class GraphSampler(ReplayedStep):
         self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw)
         if fused:
             return
+        if self.multistep:
+            nat.update_ms_x0(pl.x_in, pl.out, self.pred, self.t_buf, recip, recipm1, c1, c2, sg, mean_type, self.clip, pl.x_in,
+                             self.pred)
+            return
         if in_kernel:
             nat.update_rng_x0(pl.x_in, pl.out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
                               mean_type, self.clip, pl.x_in, None if det else self.seed, self.pred)
@@ -946,6 +1057,8 @@ class GraphSampler(ReplayedStep):
             self.fall_back()
         self._begin_chain(img, model_kwargs)
         self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
+        if self.multistep:
+            self.pred.zero_()                               # no history (k3 = 0 at the chain's first step: it is not read)
 
     def fall_back(self):
         super().fall_back()
@@ -971,7 +1084,14 @@ class GraphSampler(ReplayedStep):
     def _state(self):
         return {"sample": self.plan.x_in, "pred_xstart": self.pred, "attn": None}
 
+    def _check_order(self, i):
+        """A multistep chain walks consecutive timesteps (its history is the step before); n - 1 starts a chain over."""
+        if self.multistep and i != self.expected_t and i != self.diffusion.num_timesteps - 1:
+            raise ValueError(f"the multistep rule {self.rule!r} walks consecutive timesteps: expected t = {self.expected_t} "
+                             f"(or {self.diffusion.num_timesteps - 1}, a new chain), got {i}")
+
     def step(self, i):
+        self._check_order(i)
         super().step(i)
         return self._state()
 
@@ -980,6 +1100,7 @@ class GraphSampler(ReplayedStep):
         (chain seed, t, element), the clock lives on the device - but K steps per graph launch while at least K remain."""
         if self.inject_noise and n > 1:
             raise ValueError("inject_noise: the caller provides the noise of every step - use step()")
+        self._check_order(i)
         if i != self.expected_t:
             self.t_buf.fill_(i + 1)
         left, t = int(n), int(i)

@@ -64,6 +64,9 @@ class SpacedDiffusion(GaussianDiffusion):
     def ddim_reverse_sample(self, model, *args, **kwargs):
         return super().ddim_reverse_sample(self._wrap_model(model), *args, **kwargs)
 
+    def dpm_solver_sample(self, model, *args, **kwargs):
+        return super().dpm_solver_sample(self._wrap_model(model), *args, **kwargs)
+
     def _wrap_model(self, model):
         if isinstance(model, _WrappedModel):
             return model

@@ -1,6 +1,6 @@
 """Windowed long-video sampling: fill a (B, T, C, H, W) video window by window, each window one
-``p_sample_loop`` (``args.use_ddim``: ``ddim_sample_loop`` with ``eta = args.ddim_eta``) over at most ``max_frames`` frames
-chosen by a sampling scheme.
+``p_sample_loop`` (``args.use_ddim``: ``ddim_sample_loop`` with ``eta = args.ddim_eta``; ``args.use_dpm_solver``:
+``dpm_solver_sample_loop``) over at most ``max_frames`` frames chosen by a sampling scheme.
 
 Behaviour of ``sample_video`` in the reference's scripts/video_sample.py:28-85 (same arguments, same return
 value), restructured for the MI355X path:
@@ -38,10 +38,14 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
 
     args needs: n_obs, max_frames, max_latent_frames, sampling_scheme, clip_denoised, device and optionally
     optimality / eval_dir (an ``optimal_schedule.pt`` under eval_dir), use_ddim / ddim_eta (DDIM instead of the ancestral
-    chain; in the reference ``--use_ddim`` only renames the results folder, here it selects the sampler).  Returns ``(samples, indices_used)``
+    chain; in the reference ``--use_ddim`` only renames the results folder, here it selects the sampler), use_dpm_solver
+    (DPM-Solver++(2M) instead; together with use_ddim: ValueError).  Returns ``(samples, indices_used)``
     with ``samples`` on batch's device and ``indices_used`` the list of (obs, latent) index lists per window.
     """
     B, T = batch.shape[:2]
+    use_dpm_solver = bool(getattr(args, "use_dpm_solver", False))
+    if use_dpm_solver and getattr(args, "use_ddim", False):
+        raise ValueError("use_ddim and use_dpm_solver select different samplers: set one of them")
     device = th.device(args.device)
     samples = th.zeros_like(batch, device=device)
     samples[:, :args.n_obs] = batch[:, :args.n_obs].to(device)
@@ -66,6 +70,11 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
         n_lat = len(lat_idx[0])
         if just_get_indices:
             local = batch_dev[rows, frame_indices]
+        elif use_dpm_solver:
+            local = diffusion.dpm_solver_sample_loop(
+                model, tuple(x0.shape), clip_denoised=args.clip_denoised,
+                model_kwargs=dict(frame_indices=frame_indices, x0=x0, obs_mask=obs_mask, latent_mask=latent_mask),
+                latent_mask=latent_mask, return_decoded=decoded)
         elif getattr(args, "use_ddim", False):
             local = diffusion.ddim_sample_loop(
                 model, tuple(x0.shape), clip_denoised=args.clip_denoised,
@@ -84,8 +93,11 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
 def default_sampling_args(**kw):
     """Namespace with the defaults of the reference CLI (video_sample.py:171-192) for programmatic use."""
     d = dict(sampling_scheme="autoreg", n_obs=36, max_frames=20, max_latent_frames=None, clip_denoised=True,
-             optimality=None, eval_dir=None, use_ddim=False, ddim_eta=0.0, device="cuda" if th.cuda.is_available() else "cpu")
+             optimality=None, eval_dir=None, use_ddim=False, ddim_eta=0.0, use_dpm_solver=False,
+             device="cuda" if th.cuda.is_available() else "cpu")
     d.update(kw)
+    if d["use_ddim"] and d["use_dpm_solver"]:
+        raise ValueError("use_ddim and use_dpm_solver select different samplers: set one of them")
     if d["max_latent_frames"] is None:
         d["max_latent_frames"] = d["max_frames"] // 2
     return SimpleNamespace(**d)
