@@ -676,6 +676,30 @@ typedef struct lfvdm_adamw_args {
 int lfvdm_adamw_ema(const lfvdm_adamw_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Global-norm gradient clipping and the non-finite step skip (torch.nn.utils.clip_grad_norm_ in front of opt.step()),
+ * three launches on one stream and no host synchronisation:  partials -> finalize -> lfvdm_adamw_ema_clip.
+ *
+ * lfvdm_grad_norm_partials: partials[w] = the sum of (grad_scale*g[i])^2 over the elements workgroup w visits (grid-stride
+ *   16-byte loads; scalar head / tail for a `g` that does not start on a 16-byte boundary / an n that is no multiple of 4;
+ *   `g` must be 4-byte aligned).  nparts must equal lfvdm_grad_norm_nparts(n) - the grid, a function of n alone
+ *   (<= LFVDM_GRAD_NORM_MAX_PARTS) - and `partials` holds that many floats.
+ * lfvdm_grad_norm_finalize: one workgroup adds the partials in index order in double and writes the 16-byte record `stat`:
+ *   stat[0] fp32   squared norm (before clipping)
+ *   stat[1] fp32   coef = min(1, max_norm / (norm + 1e-6)), 1 for max_norm <= 0 (0 when stat[2] is set)
+ *   stat[2] int32  1 if the squared norm is inf or NaN, else 0
+ *   stat[3] int32  += stat[2]: running count of skipped steps (the caller zeroes the record once)
+ * lfvdm_adamw_ema_clip: lfvdm_adamw_ema with the gradient multiplied by a->grad_scale * stat[1]; stat[2] != 0 makes the
+ *   launch a no-op exactly like the skip_flag words (which are honoured as well): nothing is read or written.
+ *   a->grad_sqsum is ignored - the norm is stat[0].  lfvdm_adamw_args is the same struct.
+ * No float atomics, no arrival counter: fixed summation order, bitwise reproducible with or without LFVDM_DETERMINISTIC.
+ * ------------------------------------------------------------------------------------- */
+#define LFVDM_GRAD_NORM_MAX_PARTS 512
+int lfvdm_grad_norm_nparts(int64_t n);
+int lfvdm_grad_norm_partials(const float* g, int64_t n, float grad_scale, float* partials, int nparts, void* stream);
+int lfvdm_grad_norm_finalize(const float* partials, int nparts, float max_norm, float* stat, void* stream);
+int lfvdm_adamw_ema_clip(const lfvdm_adamw_args* a, const float* stat, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training-batch assembly on the device (TrainLoop.prepare_training_batch, train_util.py:224-241, with the masks of
  * sample_all_masks, :193-222).  The host samples the index table (same sequence of random draws as the reference);
  * the gather and the mask / index tensors are produced here, inside the captured training step.

@@ -179,6 +179,10 @@ _SIGS = {
     "lfvdm_attn_spatial_bwd": ([c_fp] * 6 + [c_i, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_attn_temporal": ([c_fp] * 7 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_adamw_ema": ([C.POINTER(AdamWArgs), c_fp], c_i),
+    "lfvdm_grad_norm_nparts": ([C.c_int64], c_i),
+    "lfvdm_grad_norm_partials": ([c_fp, C.c_int64, C.c_float, c_fp, c_i, c_fp], c_i),
+    "lfvdm_grad_norm_finalize": ([c_fp, c_i, C.c_float, c_fp, c_fp], c_i),
+    "lfvdm_adamw_ema_clip": ([C.POINTER(AdamWArgs), c_fp, c_fp], c_i),
     "lfvdm_q_sample": ([c_fp] * 6 + [c_i, c_i, c_fp], c_i),
     "lfvdm_masked_mse": ([c_fp] * 4 + [c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_prepare_batch": ([c_fp] * 6 + [c_i] * 4 + [c_fp], c_i),
@@ -732,6 +736,28 @@ def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):
 
 def masked_mse(a, b, mask, out, B, T, frame_inner):
     check(lib().lfvdm_masked_mse(ptr(a), ptr(b), ptr(mask), ptr(out), B, T, frame_inner, stream()), "lfvdm_masked_mse")
+
+
+def grad_norm_nparts(n):
+    """Workgroups of lfvdm_grad_norm_partials for an arena of n floats = floats of its scratch (a function of n alone)."""
+    return int(lib().lfvdm_grad_norm_nparts(int(n)))
+
+
+def grad_clip_stat(g, grad_scale, max_norm, partials, stat):
+    """stat (4 x fp32) <- {squared norm of grad_scale*g, clip coefficient, non-finite flag, += skipped count}: the two norm
+    launches in front of ``adamw_ema_clip``.  g: 1-D fp32 (any 4-byte alignment); partials: grad_norm_nparts(g.numel()) floats."""
+    n = g.numel()
+    if partials.numel() != grad_norm_nparts(n) or stat.numel() != 4:
+        raise RuntimeError("grad_clip_stat: partials must hold grad_norm_nparts(n) floats and stat four")
+    check(lib().lfvdm_grad_norm_partials(ptr(g), n, float(grad_scale), ptr(partials), partials.numel(), stream()),
+          "lfvdm_grad_norm_partials")
+    check(lib().lfvdm_grad_norm_finalize(ptr(partials), partials.numel(), float(max_norm), ptr(stat), stream()),
+          "lfvdm_grad_norm_finalize")
+
+
+def adamw_ema_clip(a, stat):
+    """lfvdm_adamw_ema on an AdamWArgs with the clip record of ``grad_clip_stat`` applied."""
+    check(lib().lfvdm_adamw_ema_clip(C.byref(a), ptr(stat), stream()), "lfvdm_adamw_ema_clip")
 
 
 class StreamFlags:

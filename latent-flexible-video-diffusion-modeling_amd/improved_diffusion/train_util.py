@@ -39,6 +39,25 @@ except ImportError:  # optional
 INITIAL_LOG_LOSS_SCALE = 20.0
 
 
+def resolve_max_grad_norm(keyword=None, args=None):
+    """Global-norm clipping threshold of ``TrainLoop``: the ``max_grad_norm`` keyword, else ``args.max_grad_norm``, else the
+    environment's LFVDM_MAX_GRAD_NORM, else 0 = off (no clipping and no non-finite skip).  Negative or non-finite: ValueError."""
+    value = keyword
+    if value is None:
+        value = getattr(args, "max_grad_norm", None)
+    if value is None:
+        value = os.environ.get("LFVDM_MAX_GRAD_NORM") or None
+    if value is None:
+        return 0.0
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_grad_norm must be a number >= 0, got {value!r}") from None
+    if not math.isfinite(value) or value < 0:
+        raise ValueError(f"max_grad_norm must be finite and >= 0 (0 = off), got {value!r}")
+    return value
+
+
 class ParamArena:
     """Flat fp32 storage for a list of parameters: ``p.data`` and ``p.grad`` become views of two
     contiguous buffers, which gives one collective per bucket, one fused optimizer launch and a memset for
@@ -85,10 +104,12 @@ class ParamArena:
 class TrainLoop:
     def __init__(self, *, model, diffusion, data, batch_size, microbatch, lr, ema_rate, log_interval, save_interval,
                  resume_checkpoint, use_fp16, diffusion_space_kwargs, fp16_scale_growth, schedule_sampler, weight_decay,
-                 lr_anneal_steps, sample_interval, pad_with_random_frames, max_frames, enc_dec_chunk_size, args):
+                 lr_anneal_steps, sample_interval, pad_with_random_frames, max_frames, enc_dec_chunk_size, args,
+                 max_grad_norm=None):
         if use_fp16:
             raise NotImplementedError("use_fp16 is off in the reference defaults; the native path is fp32")
         self.args = args
+        self.max_grad_norm = resolve_max_grad_norm(max_grad_norm, args)     # 0: no clipping, no non-finite skip
         dist_util.limit_host_threads()
         self.model = model
         self.diffusion = diffusion
@@ -159,6 +180,11 @@ class TrainLoop:
             self.ema_flat.append(flat)
         self.ema_params = [self.arena.views(f) for f in self.ema_flat]
         self.grad_sqsum = th.zeros(1, device=dev)
+        # clip record {squared norm, coefficient, non-finite flag (int32), skipped steps (int32)}: written by
+        # lfvdm_grad_norm_finalize on the device, by _optimize_host for arenas in host memory; zeroed once, here
+        self.clip_stat = th.zeros(4, device=dev)
+        self.clip_partials = (th.empty(nat.grad_norm_nparts(self.arena.numel), device=dev)
+                              if self.max_grad_norm > 0 and dev.type == "cuda" else None)
         self._graph_state = {}
 
         self.use_ddp = exchanging
@@ -545,13 +571,25 @@ class TrainLoop:
 
     def optimize_normal(self):
         """Bucketed all-reduce (overlapped with the tail of the backward pass) + fused AdamW/EMA/grad-norm
-        (reference train_util.py:346-357; the exchange is DDP's there, :116-125)."""
+        (reference train_util.py:346-357; the exchange is DDP's there, :116-125).
+
+        ``max_grad_norm`` > 0 adds global-norm clipping (torch.nn.utils.clip_grad_norm_'s formula) and the non-finite skip:
+        two norm launches write the clip record on the device (``clip_stat``), the optimizer launch scales the gradient by its
+        coefficient and is a no-op when the norm is inf or NaN - parameters, moments and EMA copies keep their values.  All
+        three run on the stream that has just joined the bucket all-reduces, so the norm is that of the AVERAGED gradient,
+        bitwise the same on every rank: coefficient and skip are agreed without another collective.  The host never learns of
+        a skip without a synchronisation, so ``opt_step`` (Adam's bias correction) advances on a skipped step too; the count
+        of skipped steps is logged as ``skipped_nonfinite_steps`` wherever ``grad_norm`` is."""
         if self.use_ddp:
             self.exchange.launch()      # RCCL SUM per bucket on the side stream; averaged by grad_scale below
             self.exchange.wait()
         self._anneal_lr()
         self.opt_step += 1
-        self.grad_sqsum.zero_()
+        if not self.arena.p.is_cuda:
+            return self._optimize_host()
+        clip = self.max_grad_norm > 0
+        if not clip:
+            self.grad_sqsum.zero_()
         a = nat.AdamWArgs()
         a.p, a.g, a.m, a.v = self.arena.p.data_ptr(), self.arena.g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
         for i, (flat, rate) in enumerate(zip(self.ema_flat, self.ema_rate)):
@@ -562,11 +600,15 @@ class TrainLoop:
         a.bias_corr1 = 1.0 - self.betas[0] ** self.opt_step
         a.bias_corr2_sqrt = math.sqrt(1.0 - self.betas[1] ** self.opt_step)
         a.grad_scale = 1.0 / self.world
-        a.grad_sqsum = self.grad_sqsum.data_ptr()
+        a.grad_sqsum = None if clip else self.grad_sqsum.data_ptr()
         a.skip_flag = self.exchange.skip_flag_ptr()     # a timed-out bucket wait turns this launch into a no-op ...
         a.skip_flag2 = self.exchange.skip_word_ptr()    # ... on every rank: the word that rode in the last bucket
-        import ctypes
-        nat.check(nat.lib().lfvdm_adamw_ema(ctypes.byref(a), nat.stream()), "lfvdm_adamw_ema")
+        if clip:
+            nat.grad_clip_stat(self.arena.g, a.grad_scale, self.max_grad_norm, self.clip_partials, self.clip_stat)
+            nat.adamw_ema_clip(a, self.clip_stat)
+        else:
+            import ctypes
+            nat.check(nat.lib().lfvdm_adamw_ema(ctypes.byref(a), nat.stream()), "lfvdm_adamw_ema")
         self._invalidate_engine()
         try:
             self.exchange.poll_timeout()         # every step: the words of the PREVIOUS step, read through pinned memory
@@ -574,8 +616,53 @@ class TrainLoop:
             self.opt_step -= getattr(self.exchange, "skipped_steps", 0)      # bias correction counts applied steps only
             raise
         if self.step % self.log_interval == 0:   # the only host sync of the optimizer phase
-            logger.logkv_mean("grad_norm", float(np.sqrt(self.grad_sqsum.item())))
+            self._log_grad_norm()
             self.exchange.poll_timeout(sync=True)
+
+    def _log_grad_norm(self):
+        """``grad_norm`` (before clipping) and, with clipping on, ``grad_clip_coef`` / ``skipped_nonfinite_steps``: one
+        device->host read, at the place the reference logs its gradient norm."""
+        if self.max_grad_norm > 0:
+            st = self.clip_stat.cpu()
+            logger.logkv_mean("grad_norm", float(np.sqrt(st[0].item())))
+            logger.logkv_mean("grad_clip_coef", float(st[1].item()))
+            logger.logkv("skipped_nonfinite_steps", int(st.view(th.int32)[3].item()))
+        else:
+            logger.logkv_mean("grad_norm", float(np.sqrt(self.grad_sqsum.item())))
+
+    def _optimize_host(self):
+        """``optimize_normal`` for arenas in HOST memory (no GPU in the process; the U-Net itself runs on the device only):
+        the arithmetic of the fused launches in torch, so that the clipping semantics can be checked on any machine -
+        torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False) on the averaged gradient, a skipped step when its norm is
+        inf or NaN, torch.optim.AdamW's update on the flat arenas, EMA.  Arenas on the device never come here."""
+        g = self.arena.g
+        if self.world > 1:
+            g.mul_(1.0 / self.world)
+        stat_i = self.clip_stat.view(th.int32)
+        with th.no_grad():
+            if self.max_grad_norm > 0:
+                norm = th.nn.utils.clip_grad_norm_(self.model_params, self.max_grad_norm, error_if_nonfinite=False)
+                self.clip_stat[0] = norm.float() ** 2
+                bad = not bool(th.isfinite(self.clip_stat[0]))
+                self.clip_stat[1] = 0.0 if bad else min(1.0, self.max_grad_norm / (float(norm) + 1e-6))
+                stat_i[2] = int(bad)
+                stat_i[3] += int(bad)
+                if bad:
+                    return
+            else:
+                self.grad_sqsum[0] = float(g.double().pow(2).sum())
+            lr, (b1, b2) = self.cur_lr(), self.betas
+            p, m, v = self.arena.p, self.exp_avg, self.exp_avg_sq
+            p.mul_(1.0 - lr * self.weight_decay)
+            m.mul_(b1).add_(g, alpha=1.0 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+            denom = v.sqrt().div_(math.sqrt(1.0 - b2 ** self.opt_step)).add_(self.adam_eps)
+            p.addcdiv_(m, denom, value=-lr / (1.0 - b1 ** self.opt_step))
+            for flat, rate in zip(self.ema_flat, self.ema_rate):
+                flat.mul_(rate).add_(p, alpha=1.0 - rate)
+        self._invalidate_engine()
+        if self.step % self.log_interval == 0:
+            self._log_grad_norm()
 
     def _invalidate_engine(self):
         nat.param_epoch[0] += 1          # cached packed weights (sampler plans, training path) are stale now
