@@ -261,7 +261,11 @@ LOCAL_CASES = {
     "down2x4_to_1x2": (40, 2, 4, 1, 2, 3, 2, 0, 128, 0, 0, 0, 128, True, (False, 0, 0, 0), 1),
     "map1x1_gw8": (40, 1, 1, 1, 1, 3, 1, 0, 64, 0, 0, 0, 256, True, (True, 0, 0, 0), 1),
     "down2x2_to_1x1_rt2_ragged": (23, 2, 2, 1, 1, 3, 2, 0, 128, 0, 0, 0, 128, False, (True, 1, 0, 0), 2),
+    # off centre through the bias (+-64 alternating per group, conv output std about 0.05): the GroupNorm statistics of the
+    # stage see |mean| / std of about 1280 while the conv itself stays well conditioned (test_conditioning_*)
+    "off_centre_bias_4x4": (40, 4, 4, 4, 4, 3, 1, 0, 128, 0, 0, 0, 128, False, (True, 1, 0, 0), 1),
 }
+OFF_CENTRE_LOCAL = {"off_centre_bias_4x4": (64.0, 0.05)}
 
 
 def _local_stage_f64(N, Hs, Ws, Ho, Wo, k, stride, up, src0, src1, W, b, s2a, s2b, W2, b2, resid, gn, gamma, beta, film, T):
@@ -293,6 +297,41 @@ def _local_stage_f64(N, Hs, Ws, Ho, Wo, k, stride, up, src0, src1, W, b, s2a, s2
     return y, F.silu(g).reshape(N * Ho * Wo, Cout)
 
 
+def _local_inputs(name, dev):
+    """The operands of one LOCAL_CASES stage (seeded by the case's name) on ``dev``."""
+    import zlib
+    N, Hs, Ws, Ho, Wo, k, stride, up, C0, C1, s2C0, s2C1, Cout, res, gn, rt = LOCAL_CASES[name]
+    T = 2 if N % 2 == 0 else 1
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
+    rn = lambda *s: torch.randn(*s, generator=g).to(dev)      # noqa: E731
+    Cin, C2, taps = C0 + C1, s2C0 + s2C1, k * k
+    M, Min = N * Ho * Wo, N * Hs * Ws
+    src0, src1 = rn(Min, C0), (rn(Min, C1) if C1 else None)
+    W, b = rn(Cout, taps, Cin) / (taps * Cin) ** 0.5, 0.1 * rn(Cout)
+    s2a, s2b = (rn(M, s2C0) if s2C0 else None), (rn(M, s2C1) if s2C1 else None)
+    W2, b2 = (rn(Cout, C2) / C2 ** 0.5 if C2 else None), (0.1 * rn(Cout) if C2 else None)
+    resid = rn(M, Cout) if res else None
+    gamma, beta, film = 1.0 + 0.1 * rn(Cout), 0.1 * rn(Cout), 0.3 * rn(N // T, 2 * Cout)
+    if name in OFF_CENTRE_LOCAL:
+        mean, std = OFF_CENTRE_LOCAL[name]
+        gw = (gn[2] or Cout // 32)
+        sign = (1.0 - 2.0 * ((torch.arange(Cout) // gw) % 2).float()).to(dev)
+        W, b = (W * std).contiguous(), mean * sign + std * b
+    return src0, src1, W, b, s2a, s2b, W2, b2, resid, gamma, beta, film
+
+
+def local_stage_budget(name):
+    """(fp64 raw rows, fp64 normalised rows, budget) of an OFF_CENTRE_LOCAL case: the bound of test_conditioning_gpu (4 x the
+    float32 two-pass model + this test's 1e-4) in place of the fixed tolerance.  CPU only."""
+    from test_conditioning_gpu import computed_budget, _affine
+    N, Hs, Ws, Ho, Wo, k, stride, up, C0, C1, s2C0, s2C1, Cout, res, gn, rt = LOCAL_CASES[name]
+    T = 2 if N % 2 == 0 else 1
+    src0, src1, W, b, s2a, s2b, W2, b2, resid, gamma, beta, film = _local_inputs(name, "cpu")
+    raw, ref = _local_stage_f64(N, Hs, Ws, Ho, Wo, k, stride, up, src0, src1, W, b, s2a, s2b, W2, b2, resid, gn, gamma, beta, film, T)
+    post = lambda r: _affine(r, N, Ho * Wo, Cout, gamma, beta, film if gn[0] else None, T, 1)      # noqa: E731
+    return raw, ref, computed_budget(raw, N, Ho * Wo, Cout, gn[2] or Cout // 32, post, ref, 1e-4)
+
+
 @pytest.mark.parametrize("name", sorted(LOCAL_CASES))
 def test_sample_local_stage_matches_the_tile_kernel(name):
     """One LFVDM_CHAIN_LOCAL stage (csrc/conv_local_body.h: whole samples x 16 filters x all of K per work item, MFMA
@@ -305,17 +344,8 @@ def test_sample_local_stage_matches_the_tile_kernel(name):
     from improved_diffusion import _native as nat
     N, Hs, Ws, Ho, Wo, k, stride, up, C0, C1, s2C0, s2C1, Cout, res, gn, rt = LOCAL_CASES[name]
     T = 2 if N % 2 == 0 else 1
-    import zlib
-    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
-    rn = lambda *s: torch.randn(*s, generator=g).cuda()      # noqa: E731
-    Cin, C2, taps = C0 + C1, s2C0 + s2C1, k * k
-    M, Min = N * Ho * Wo, N * Hs * Ws
-    src0, src1 = rn(Min, C0), (rn(Min, C1) if C1 else None)
-    W, b = rn(Cout, taps, Cin) / (taps * Cin) ** 0.5, 0.1 * rn(Cout)
-    s2a, s2b = (rn(M, s2C0) if s2C0 else None), (rn(M, s2C1) if s2C1 else None)
-    W2, b2 = (rn(Cout, C2) / C2 ** 0.5 if C2 else None), (0.1 * rn(Cout) if C2 else None)
-    resid = rn(M, Cout) if res else None
-    gamma, beta, film = 1.0 + 0.1 * rn(Cout), 0.1 * rn(Cout), 0.3 * rn(N // T, 2 * Cout)
+    Cin, C2, M = C0 + C1, s2C0 + s2C1, N * Ho * Wo
+    src0, src1, W, b, s2a, s2b, W2, b2, resid, gamma, beta, film = _local_inputs(name, "cuda")
     ref_raw, ref_gn = _local_stage_f64(N, Hs, Ws, Ho, Wo, k, stride, up, src0, src1, W, b, s2a, s2b, W2, b2, resid, gn, gamma,
                                        beta, film, T)
     outs = []
@@ -364,12 +394,17 @@ def test_sample_local_stage_matches_the_tile_kernel(name):
     else:
         assert bool((r1 == 7.0).all()), "gn_skip_raw: the raw tensor is not written"
     if gn:
+        limit = 1e-4
         tol = 2e-5 * (1.0 + float(g0.abs().max()))
+        if name in OFF_CENTRE_LOCAL:        # each form within the conditioning bound of fp64, so within twice that of each other
+            bud = local_stage_budget(name)[2]
+            limit, tol = bud["bound"], 2 * bud["bound"]
+            print(f"[cond] local stage {name}: two-pass model {bud['two']:.3e}, one-pass model {bud['one']:.3e}, bound {limit:.3e}")
         devs = {"local-tile": float((g0[:, :Cout] - g1[:, :Cout]).abs().max())}
         for which, gg in (("tile", g0), ("local", g1)):
             devs[which] = float((gg[:, :Cout].double().cpu() - ref_gn).abs().max())
         print(f"[local] {name}: P = {Ho * Wo}, normalised max|d| " + ", ".join(f"{k_} {v:.3g}" for k_, v in devs.items()))
         assert float((g0 - g1).abs().max()) <= tol, (name, devs)
-        assert devs["tile"] <= 1e-4 and devs["local"] <= 1e-4, (name, devs)
+        assert devs["tile"] <= limit and devs["local"] <= limit, (name, devs)
         if gn[3]:
             assert bool((g1[:, Cout:] == 7.0).all()), "the other half of the concat operand is someone else's"

@@ -666,7 +666,7 @@ def test_gn_apply_large_maps(nat, N, P, C0, C1, film, act):
     registers (chunk statistics + fixed-order combination), ragged last chunks and non-power-of-two channel quads included;
     the last case fits and must take the single-launch kernel (workspace size 0)."""
     C, T = C0 + C1, 2
-    a = rnd("gl/a", N * P, C0) * 1.3 + 0.7          # a mean well away from zero: a naive sum of squares would show
+    a = rnd("gl/a", N * P, C0) * 1.3 + 0.7          # |mean| / std of 0.5: a one-pass E[x^2] - mean^2 would still pass (test_conditioning_*)
     b = rnd("gl/b", N * P, C1) if C1 else None
     gamma, beta = 1 + 0.1 * rnd("gl/g", C), 0.1 * rnd("gl/be", C)
     fm = 0.3 * rnd("gl/film", N // T, 2 * C) if film else None
