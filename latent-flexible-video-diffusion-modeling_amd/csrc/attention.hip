@@ -9,6 +9,7 @@
 //                        (no LDS round trip for P); softmax reductions are wave shuffles.
 //  * attn_temporal     : one wave per (batch, pixel, head); T <= 32 frames attend with the three
 //                        RPE terms and the two-clique mask (rpe.py:143-169) on the VALU.
+#include "attention_temporal.h"
 #include "common_hip.h"
 
 namespace {
@@ -472,8 +473,7 @@ __global__ __launch_bounds__(256) void attn_spatial_probs_kernel(const float* __
 // - [T][T][FC], shared by every pixel - are staged ONCE per workgroup in LDS (R_q transposed to [t][s]), the
 // k (then v) rows of the wave's pixels wave-privately; q stays in registers.  Rows are padded by 4 floats:
 // lanes of consecutive t read b128 words 4 banks apart (conflict-free), lanes of one pixel share k/v words
-// (LDS broadcast).  TMAX bounds the unrolled key loop (T <= TMAX).
-constexpr int TA_MAXT = 32;
+// (LDS broadcast).  TMAX bounds the unrolled key loop (T <= TMAX <= TEMPORAL_MAXT, attention_temporal.h).
 
 // The kernel is a short pipeline of phases: NC logit chunks, then NC PV chunks.  The global loads of phase
 // i+1 are issued into registers BEFORE phase i computes (the loop over chunks is latency-bound otherwise:
@@ -687,28 +687,26 @@ void attn_temporal_kernel(const float* __restrict__ qkv, const float* __restrict
 }
 
 template <int TMAX, int FC>
-int launch_temporal(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
-                    float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s) {
-    const int PPW = 64 / T;                                  // pixels per wave
-    const int RST = T * FC + 4;
-    const size_t lds = (size_t)(2 * T + 4 * PPW) * RST * sizeof(float);
+int launch_temporal(const TemporalFwd& a) {
+    const int PPW = 64 / a.T;                                // pixels per wave
+    const int RST = a.T * FC + 4;
+    const size_t lds = (size_t)(2 * a.T + 4 * PPW) * RST * sizeof(float);
     if (lds > 160 * 1024) return LFVDM_E_UNSUPPORTED;
     static DynLdsLimit limit;       // raised (per device) when a larger T needs it
     if (int rc = limit.ensure(reinterpret_cast<const void*>(&attn_temporal_kernel<TMAX, FC>), lds)) return rc;
-    const dim3 grid((unsigned)((P + 4 * PPW - 1) / (4 * PPW)), (unsigned)heads, (unsigned)B);
-    hipLaunchKernelGGL((attn_temporal_kernel<TMAX, FC>), grid, dim3(256), lds, s, qkv, Rq, Rk, Rv, mask, o, attn_out, T, P, C,
-                       heads, PPW, rsel);
+    const dim3 grid((unsigned)((a.P + 4 * PPW - 1) / (4 * PPW)), (unsigned)a.heads, (unsigned)a.B);
+    hipLaunchKernelGGL((attn_temporal_kernel<TMAX, FC>), grid, dim3(256), lds, a.s, a.qkv, a.Rq, a.Rk, a.Rv, a.mask, a.o,
+                       a.attn_out, a.T, a.P, a.C, a.heads, PPW, a.rsel);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
 
 template <int FC>
-int launch_temporal_t(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
-                      float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s) {
-    if (T <= 8) return launch_temporal<8, FC>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (T <= 16) return launch_temporal<16, FC>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (T <= 24) return launch_temporal<24, FC>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    return launch_temporal<32, FC>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
+int launch_temporal_t(const TemporalFwd& a) {
+    if (a.T <= 8) return launch_temporal<8, FC>(a);
+    if (a.T <= 16) return launch_temporal<16, FC>(a);
+    if (a.T <= 24) return launch_temporal<24, FC>(a);
+    return launch_temporal<32, FC>(a);
 }
 
 }  // namespace
@@ -799,37 +797,29 @@ extern "C" int lfvdm_attn_spatial_bwd(const float* qkv, const float* o, const fl
     return LFVDM_OK;
 }
 
-int lfvdm_attn_temporal2_try(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
-                             float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s);
-// (attention_temporal_long.hip) 33 <= T <= 64 frames; LFVDM_E_UNSUPPORTED = head dim not a multiple of 8
-int lfvdm_attn_temporal_long(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
-                             float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s);
-constexpr int TA_MAXT_LONG = 64;
-
 extern "C" int lfvdm_attn_temporal_ring(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask,
                                         float* o, float* attn_out, int B, int T, int P, int C, int heads, const int64_t* rsel_p,
                                         int ring, void* stream) {
-    if (B <= 0 || T <= 0 || T > TA_MAXT_LONG || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
+    if (B <= 0 || T <= 0 || T > TEMPORAL_MAXT_LONG || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
     if (!Rq || !Rk || !Rv || ring < 0 || (ring > 0 && !rsel_p)) return LFVDM_E_SHAPE;
-    const RSel rsel = {rsel_p, ring};
+    const TemporalFwd a = {qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, RSel{rsel_p, ring}, (hipStream_t)stream};
     const int F = C / heads;
-    hipStream_t s = (hipStream_t)stream;
     // long windows (33..64 frames): frame-group kernel (attention_temporal_long.hip); T <= 32 below, unchanged
-    if (T > TA_MAXT) return lfvdm_attn_temporal_long(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
+    if (T > TEMPORAL_MAXT) return lfvdm_attn_temporal_long(a);
     // second-generation kernel (attention_temporal2.hip) for head dims 16 / 32 / 64 and launches that do not fill the chip
     {
-        const int rc = lfvdm_attn_temporal2_try(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
+        const int rc = lfvdm_attn_temporal2_try(a);
         if (rc != LFVDM_E_UNSUPPORTED) return rc;
     }
     // head dim 32 (the 128-channel levels): the whole head in ONE chunk - two staging phases instead of four.  The R
     // slices of a chunk are then 2 x T x (32T + 4) floats: fits the 160 KiB of LDS up to T = 24 (launch_temporal checks)
     static const bool no_fc32 = getenv("LFVDM_ATTN_NO_FC32") != nullptr;      // A/B aid
     if (F == 32 && T <= 24 && !no_fc32) {
-        const int rc = launch_temporal_t<32>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
+        const int rc = launch_temporal_t<32>(a);
         if (rc != LFVDM_E_UNSUPPORTED) return rc;
     }
-    if (F % 16 == 0 && T <= 24) return launch_temporal_t<16>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (F % 8 == 0) return launch_temporal_t<8>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
+    if (F % 16 == 0 && T <= 24) return launch_temporal_t<16>(a);
+    if (F % 8 == 0) return launch_temporal_t<8>(a);
     return LFVDM_E_UNSUPPORTED;
 }
 

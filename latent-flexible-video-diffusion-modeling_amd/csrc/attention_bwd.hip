@@ -18,23 +18,11 @@
 
 #include <cstdlib>
 
+#include "attention_temporal.h"   // the argument record, the frame limits and the second-generation / long-window entries
 #include "common_hip.h"
 #include "lfvdm_hip.h"
 
-// (attention_temporal2.hip) the rows kernel in the second-generation decomposition; LFVDM_E_UNSUPPORTED = not covered
-int lfvdm_attn_temporal2_bwd_rows_try(const float* qkv, const float* dO, const float* Rq, const float* Rk, const float* Rv,
-                                      const float* mask, float* dqkv, float* Pg, float* dSg, int B, int T, int P, int C, int heads,
-                                      hipStream_t s);
-
-// (attention_temporal_long.hip) rows + cols kernels for 33 <= T <= 64 frames; LFVDM_E_UNSUPPORTED = not covered
-int lfvdm_attn_temporal_long_bwd(const float* qkv, const float* d_o, const float* Rq, const float* Rk, const float* Rv,
-                                 const float* mask, float* Pg, float* dSg, float* dqkv, int B, int T, int P, int C, int heads,
-                                 hipStream_t s);
-
 namespace {
-
-constexpr int TB_MAXT = 32;
-constexpr int TB_MAXT_LONG = 64;
 
 template <int TMAX, int FC>
 struct TBStage {
@@ -671,39 +659,37 @@ __global__ __launch_bounds__(64) void rpe_nets_bwd_reduce_kernel(const lfvdm_rpe
 }
 
 template <int TMAX, int FC>
-int launch_tb(const float* qkv, const float* d_o, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* Pg,
-              float* dSg, float* dqkv, int B, int T, int P, int C, int heads, hipStream_t s) {
-    const int PPW = 64 / T;
-    const int RST = T * FC + 4;
-    const size_t lds_rows = (size_t)(2 * T + 4 * PPW) * RST * sizeof(float);
-    const size_t lds_cols = (size_t)(T + 8 * PPW) * RST * sizeof(float);
+int launch_tb(const TemporalBwd& a) {
+    const int PPW = 64 / a.T;
+    const int RST = a.T * FC + 4;
+    const size_t lds_rows = (size_t)(2 * a.T + 4 * PPW) * RST * sizeof(float);
+    const size_t lds_cols = (size_t)(a.T + 8 * PPW) * RST * sizeof(float);
     if (lds_rows > 160 * 1024 || lds_cols > 160 * 1024) return LFVDM_E_UNSUPPORTED;
     static DynLdsLimit limit_rows, limit_cols;
     if (int rc = limit_rows.ensure(reinterpret_cast<const void*>(&attn_temporal_bwd_rows_kernel<TMAX, FC>), lds_rows)) return rc;
     if (int rc = limit_cols.ensure(reinterpret_cast<const void*>(&attn_temporal_bwd_cols_kernel<TMAX, FC>), lds_cols)) return rc;
-    const dim3 grid((unsigned)((P + 4 * PPW - 1) / (4 * PPW)), (unsigned)heads, (unsigned)B);
+    const dim3 grid((unsigned)((a.P + 4 * PPW - 1) / (4 * PPW)), (unsigned)a.heads, (unsigned)a.B);
     static const bool rows_v1 = getenv("LFVDM_ATTN_BWD_ROWS_V1") != nullptr;     // A/B aid
-    int rc2 = rows_v1 ? LFVDM_E_UNSUPPORTED : lfvdm_attn_temporal2_bwd_rows_try(qkv, d_o, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
+    int rc2 = rows_v1 ? LFVDM_E_UNSUPPORTED : lfvdm_attn_temporal2_bwd_rows_try(a);
     if (rc2 == LFVDM_E_UNSUPPORTED) {
-        hipLaunchKernelGGL((attn_temporal_bwd_rows_kernel<TMAX, FC>), grid, dim3(256), lds_rows, s, qkv, d_o, Rq, Rk, Rv, mask, dqkv,
-                           Pg, dSg, T, P, C, heads, PPW);
+        hipLaunchKernelGGL((attn_temporal_bwd_rows_kernel<TMAX, FC>), grid, dim3(256), lds_rows, a.s, a.qkv, a.d_o, a.Rq, a.Rk, a.Rv,
+                           a.mask, a.dqkv, a.ws_p, a.ws_ds, a.T, a.P, a.C, a.heads, PPW);
         LFVDM_CHECK_LAUNCH();
     } else if (rc2 != LFVDM_OK) {
         return rc2;
     }
-    hipLaunchKernelGGL((attn_temporal_bwd_cols_kernel<TMAX, FC>), grid, dim3(256), lds_cols, s, qkv, d_o, Rq, Pg, dSg, dqkv, T, P,
-                       C, heads, PPW);
+    hipLaunchKernelGGL((attn_temporal_bwd_cols_kernel<TMAX, FC>), grid, dim3(256), lds_cols, a.s, a.qkv, a.d_o, a.Rq, a.ws_p, a.ws_ds,
+                       a.dqkv, a.T, a.P, a.C, a.heads, PPW);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
 
 template <int FC>
-int launch_tb_t(const float* qkv, const float* d_o, const float* Rq, const float* Rk, const float* Rv, const float* mask,
-                float* Pg, float* dSg, float* dqkv, int B, int T, int P, int C, int heads, hipStream_t s) {
-    if (T <= 8) return launch_tb<8, FC>(qkv, d_o, Rq, Rk, Rv, mask, Pg, dSg, dqkv, B, T, P, C, heads, s);
-    if (T <= 16) return launch_tb<16, FC>(qkv, d_o, Rq, Rk, Rv, mask, Pg, dSg, dqkv, B, T, P, C, heads, s);
-    if (T <= 24) return launch_tb<24, FC>(qkv, d_o, Rq, Rk, Rv, mask, Pg, dSg, dqkv, B, T, P, C, heads, s);
-    return launch_tb<32, FC>(qkv, d_o, Rq, Rk, Rv, mask, Pg, dSg, dqkv, B, T, P, C, heads, s);
+int launch_tb_t(const TemporalBwd& a) {
+    if (a.T <= 8) return launch_tb<8, FC>(a);
+    if (a.T <= 16) return launch_tb<16, FC>(a);
+    if (a.T <= 24) return launch_tb<24, FC>(a);
+    return launch_tb<32, FC>(a);
 }
 
 }  // namespace
@@ -711,22 +697,22 @@ int launch_tb_t(const float* qkv, const float* d_o, const float* Rq, const float
 extern "C" int lfvdm_attn_temporal_bwd(const float* qkv, const float* d_o, const float* Rq, const float* Rk, const float* Rv,
                                        const float* mask, float* ws_p, float* ws_ds, float* dqkv, float* dRq, float* dRk,
                                        float* dRv, int B, int T, int P, int C, int heads, void* stream) {
-    if (B <= 0 || T <= 0 || T > TB_MAXT_LONG || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
+    if (B <= 0 || T <= 0 || T > TEMPORAL_MAXT_LONG || P <= 0 || heads <= 0 || C % heads) return LFVDM_E_SHAPE;
     if (!qkv || !d_o || !Rq || !Rk || !Rv || !ws_p || !ws_ds || !dqkv || !dRq || !dRk || !dRv) return LFVDM_E_SHAPE;
     const int F = C / heads;
-    hipStream_t s = (hipStream_t)stream;
+    const TemporalBwd a = {qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, (hipStream_t)stream};
     int rc;
-    if (T > TB_MAXT) rc = lfvdm_attn_temporal_long_bwd(qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, s);
-    else if (F % 16 == 0 && T <= 24) rc = launch_tb_t<16>(qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, s);
-    else if (F % 8 == 0) rc = launch_tb_t<8>(qkv, d_o, Rq, Rk, Rv, mask, ws_p, ws_ds, dqkv, B, T, P, C, heads, s);
+    if (T > TEMPORAL_MAXT) rc = lfvdm_attn_temporal_long_bwd(a);
+    else if (F % 16 == 0 && T <= 24) rc = launch_tb_t<16>(a);
+    else if (F % 8 == 0) rc = launch_tb_t<8>(a);
     else return LFVDM_E_UNSUPPORTED;
     if (rc != LFVDM_OK) return rc;
     const dim3 grid_rpe((unsigned)T, (unsigned)heads, (unsigned)B);
-    if (T > TB_MAXT)
-        hipLaunchKernelGGL(attn_temporal_bwd_rpe_kernel<4>, grid_rpe, dim3(256), 0, s, qkv, d_o, ws_p, ws_ds, dRq, dRk, dRv, T, P, C,
+    if (T > TEMPORAL_MAXT)
+        hipLaunchKernelGGL(attn_temporal_bwd_rpe_kernel<4>, grid_rpe, dim3(256), 0, a.s, qkv, d_o, ws_p, ws_ds, dRq, dRk, dRv, T, P, C,
                            heads);
     else
-        hipLaunchKernelGGL(attn_temporal_bwd_rpe_kernel<2>, grid_rpe, dim3(256), 0, s, qkv, d_o, ws_p, ws_ds, dRq, dRk, dRv, T, P, C,
+        hipLaunchKernelGGL(attn_temporal_bwd_rpe_kernel<2>, grid_rpe, dim3(256), 0, a.s, qkv, d_o, ws_p, ws_ds, dRq, dRk, dRv, T, P, C,
                            heads);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;

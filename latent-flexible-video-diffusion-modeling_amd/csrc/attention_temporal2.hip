@@ -14,6 +14,7 @@
 //     and even the 8x8 / 2x2 levels have >= 100 workgroups;
 //   * workgroups that share 128-byte lines of R and k / v (adjacent heads when F < 32) and the frame groups of the
 //     same pixels are placed on the same XCD (blockIdx % 8), so every line is fetched by one L2 only.
+#include "attention_temporal.h"
 #include "common_hip.h"
 
 namespace {
@@ -473,10 +474,9 @@ inline size_t t2_lds_bytes(int TGN, int NPX, int RS) {
 // groups of <= 5 query frames (three pixels per wave, 15 of 16 lane quads busy, a small R image) with FOUR waves per
 // workgroup were the fastest or within 5 % of it everywhere - four waves issue the image's DMA pieces in parallel and share
 // one copy of the R slices, also where the map has fewer pixels than the workgroup has slots.  Fewer waves only when the
-// images of four do not fit the LDS.  -> false: no decomposition fits.
-inline bool t2_geometry(int B, int T, int P, int C, int heads, int F, int RS, T2Geom& g, size_t& lds, unsigned& grid) {
-    g = T2Geom{};
-    g.T = T; g.P = P; g.C = C; g.heads = heads; g.B = B;
+// images of four do not fit the LDS.  g arrives with its shape fields set.  -> the grid; 0: no decomposition fits.
+inline unsigned t2_geometry(T2Geom& g, int F, int RS, size_t& lds) {
+    const int B = g.B, T = g.T, P = g.P, heads = g.heads;
     int best_tg = (T + 4) / 5, best_nw = 0;
     {
         const int TGN = (T + best_tg - 1) / best_tg, PPW = 16 / TGN;
@@ -484,7 +484,7 @@ inline bool t2_geometry(int B, int T, int P, int C, int heads, int F, int RS, T2
             if (t2_lds_bytes(TGN, NW * PPW, RS) <= 160 * 1024) best_nw = NW;
         if (best_nw == 0) best_tg = 0;
     }
-    if (best_tg == 0) return false;
+    if (best_tg == 0) return 0;
     g.TG = best_tg; g.NW = best_nw;
     g.TGN = (T + g.TG - 1) / g.TG;
     g.PPW = 16 / g.TGN;
@@ -498,87 +498,73 @@ inline bool t2_geometry(int B, int T, int P, int C, int heads, int F, int RS, T2
     g.XPG = (g.NL <= 8 && 8 % g.NL == 0) ? 8 / g.NL : 0;
     if (g.XPG > 0) {
         const int sblks = (g.strips + g.XPG - 1) / g.XPG;
-        grid = 8u * (unsigned)(g.HL * g.TG) * (unsigned)sblks;
-    } else {
-        grid = (unsigned)(B * heads) * (unsigned)g.TG * (unsigned)g.strips;
+        return 8u * (unsigned)(g.HL * g.TG) * (unsigned)sblks;
     }
-    return true;
+    return (unsigned)(B * heads) * (unsigned)g.TG * (unsigned)g.strips;
 }
 
+// launch_t2 is overloaded on the record: the forward kernel for a TemporalFwd, the backward's rows kernel for a TemporalBwd
 template <int F, int TCAP>
-int launch_t2(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o, float* attn_out,
-              int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s) {
-    T2Geom g;
+int launch_t2(const TemporalFwd& a) {
+    T2Geom g = {a.T, a.P, a.C, a.heads, a.B};
     size_t lds;
-    unsigned grid;
-    if (!t2_geometry(B, T, P, C, heads, F, T2Cfg<F, TCAP>::RS, g, lds, grid)) return LFVDM_E_UNSUPPORTED;
+    const unsigned grid = t2_geometry(g, F, T2Cfg<F, TCAP>::RS, lds);
+    if (!grid) return LFVDM_E_UNSUPPORTED;
     static DynLdsLimit limit;
     if (int rc = limit.ensure(reinterpret_cast<const void*>(&attn_temporal2_kernel<F, TCAP>), lds)) return rc;
-    hipLaunchKernelGGL((attn_temporal2_kernel<F, TCAP>), dim3(grid), dim3(64 * g.NW), lds, s, qkv, Rq, Rk, Rv, mask, o, attn_out,
-                       rsel, g);
+    hipLaunchKernelGGL((attn_temporal2_kernel<F, TCAP>), dim3(grid), dim3(64 * g.NW), lds, a.s, a.qkv, a.Rq, a.Rk, a.Rv, a.mask, a.o,
+                       a.attn_out, a.rsel, g);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
 
 template <int F, int TCAP>
-int launch_t2_bwd_rows(const float* qkv, const float* dO, const float* Rq, const float* Rk, const float* Rv, const float* mask,
-                       float* dqkv, float* Pg, float* dSg, int B, int T, int P, int C, int heads, hipStream_t s) {
-    T2Geom g;
+int launch_t2(const TemporalBwd& a) {
+    T2Geom g = {a.T, a.P, a.C, a.heads, a.B};
     size_t lds;
-    unsigned grid;
-    if (!t2_geometry(B, T, P, C, heads, F, T2Cfg<F, TCAP>::RS, g, lds, grid)) return LFVDM_E_UNSUPPORTED;
+    const unsigned grid = t2_geometry(g, F, T2Cfg<F, TCAP>::RS, lds);
+    if (!grid) return LFVDM_E_UNSUPPORTED;
     static DynLdsLimit limit;
     if (int rc = limit.ensure(reinterpret_cast<const void*>(&attn_temporal2_bwd_rows_kernel<F, TCAP>), lds)) return rc;
-    hipLaunchKernelGGL((attn_temporal2_bwd_rows_kernel<F, TCAP>), dim3(grid), dim3(64 * g.NW), lds, s, qkv, dO, Rq, Rk, Rv, mask, dqkv,
-                       Pg, dSg, g);
+    hipLaunchKernelGGL((attn_temporal2_bwd_rows_kernel<F, TCAP>), dim3(grid), dim3(64 * g.NW), lds, a.s, a.qkv, a.d_o, a.Rq, a.Rk,
+                       a.Rv, a.mask, a.dqkv, a.ws_p, a.ws_ds, g);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
 
-template <int F>
-int launch_t2_bwd_rows_f(const float* qkv, const float* dO, const float* Rq, const float* Rk, const float* Rv, const float* mask,
-                         float* dqkv, float* Pg, float* dSg, int B, int T, int P, int C, int heads, hipStream_t s) {
-    if (T <= 8) return launch_t2_bwd_rows<F, 8>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
-    if (T <= 16) return launch_t2_bwd_rows<F, 16>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
-    if (T <= 20) return launch_t2_bwd_rows<F, 20>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
-    if (T <= 24) return launch_t2_bwd_rows<F, 24>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
-    return launch_t2_bwd_rows<F, 32>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
+// the frame-cap ladder and the head-dim ladder, written once for both records
+template <int F, class Args>
+int launch_t2_t(const Args& a) {
+    if (a.T <= 8) return launch_t2<F, 8>(a);
+    if (a.T <= 16) return launch_t2<F, 16>(a);
+    if (a.T <= 20) return launch_t2<F, 20>(a);
+    if (a.T <= 24) return launch_t2<F, 24>(a);
+    return launch_t2<F, 32>(a);
 }
 
-template <int F>
-int launch_t2_f(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
-                float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s) {
-    if (T <= 8) return launch_t2<F, 8>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (T <= 16) return launch_t2<F, 16>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (T <= 20) return launch_t2<F, 20>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (T <= 24) return launch_t2<F, 24>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    return launch_t2<F, 32>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
+template <class Args>
+int launch_t2_f(const Args& a) {
+    const int F = a.C / a.heads;
+    if (F == 16) return launch_t2_t<16>(a);
+    if (F == 32) return launch_t2_t<32>(a);
+    if (F == 64) return launch_t2_t<64>(a);
+    return LFVDM_E_UNSUPPORTED;
 }
 
 }  // namespace
 
-// Internal entry (attention.hip dispatches here first): LFVDM_E_UNSUPPORTED = shape not covered, use the first kernel.
-int lfvdm_attn_temporal2_try(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
-                             float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s) {
-    const int F = C / heads;
+// The second-generation entries of attention_temporal.h.  lfvdm_attn_temporal_ring (attention.hip) tries the forward
+// first; LFVDM_E_UNSUPPORTED = shape not covered, use the first kernel.
+int lfvdm_attn_temporal2_try(const TemporalFwd& a) {
     // Large launches (e.g. 16x16 maps at 128 channels, batch 2: 25.9 us vs 30) keep every CU busy in the first kernel
     // too, which stages each R slice once per 12 pixels instead of once per 12 pixels AND frame group: use it there.
-    if ((long)B * P * F >= 16384) return LFVDM_E_UNSUPPORTED;
-    if (F == 16) return launch_t2_f<16>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (F == 32) return launch_t2_f<32>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    if (F == 64) return launch_t2_f<64>(qkv, Rq, Rk, Rv, mask, o, attn_out, B, T, P, C, heads, rsel, s);
-    return LFVDM_E_UNSUPPORTED;
+    if ((long)a.B * a.P * (a.C / a.heads) >= 16384) return LFVDM_E_UNSUPPORTED;
+    return launch_t2_f(a);
 }
 
-// Internal entry (attention_bwd.hip tries it first): the "rows" kernel of the temporal-attention backward in the
+// launch_tb (attention_bwd.hip) tries it first: the "rows" kernel of the temporal-attention backward in the
 // second-generation decomposition; LFVDM_E_UNSUPPORTED = shape not covered, use the first-generation rows kernel.
-int lfvdm_attn_temporal2_bwd_rows_try(const float* qkv, const float* dO, const float* Rq, const float* Rk, const float* Rv,
-                                      const float* mask, float* dqkv, float* Pg, float* dSg, int B, int T, int P, int C, int heads,
-                                      hipStream_t s) {
-    const int F = C / heads;
-    if (T > 32) return LFVDM_E_UNSUPPORTED;
-    if (F == 16) return launch_t2_bwd_rows_f<16>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
-    if (F == 32) return launch_t2_bwd_rows_f<32>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
-    if (F == 64) return launch_t2_bwd_rows_f<64>(qkv, dO, Rq, Rk, Rv, mask, dqkv, Pg, dSg, B, T, P, C, heads, s);
-    return LFVDM_E_UNSUPPORTED;
+int lfvdm_attn_temporal2_bwd_rows_try(const TemporalBwd& a) {
+    if (a.T > TEMPORAL_MAXT) return LFVDM_E_UNSUPPORTED;
+    return launch_t2_f(a);
 }

@@ -21,19 +21,19 @@
 // No atomics: bitwise reproducible (deterministic mode needs nothing extra).
 #include <hip/hip_runtime.h>
 
+#include "attention_temporal.h"
 #include "common_hip.h"
 #include "lfvdm_hip.h"
 
 namespace {
 
-constexpr int TL_MAXT = 64;    // frames per window covered here
 constexpr int TL_TG = 16;      // query (rows, forward) or key (cols) frames per workgroup
 constexpr int TL_PPW = 4;      // pixels per wave (64 lanes = 4 pixels x 16 frames)
 constexpr int TL_NPX = 16;     // pixels per workgroup
 constexpr int TL_FC = 8;       // channels per staged chunk
 constexpr int TL_NQ = TL_FC / 4;
-constexpr int TL_RB = (TL_TG * TL_MAXT * TL_NQ + 255) / 256;    // float4 per thread per R image
-constexpr int TL_KB = (TL_NPX * TL_MAXT * TL_NQ + 255) / 256;   // float4 per thread per pixel image
+constexpr int TL_RB = (TL_TG * TEMPORAL_MAXT_LONG * TL_NQ + 255) / 256;    // float4 per thread per R image
+constexpr int TL_KB = (TL_NPX * TEMPORAL_MAXT_LONG * TL_NQ + 255) / 256;   // float4 per thread per pixel image
 
 struct TLGeom {
     int T, P, C, heads, F, NC, NG;    // NC = F / FC chunks, NG = frame groups
@@ -163,9 +163,9 @@ void attn_tlong_fwd_kernel(const float* __restrict__ qkv, const float* __restric
             if (sl.k_ok & (1u << i)) st4(KV + sl.k_l[i], (sl.k_in & (1u << i)) ? st.kv[i] : z);
     };
 
-    float logit[TL_MAXT];
+    float logit[TEMPORAL_MAXT_LONG];
 #pragma unroll
-    for (int s = 0; s < TL_MAXT; ++s) logit[s] = 0.f;
+    for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) logit[s] = 0.f;
 
     issue(0);
     for (int ph = 0; ph < NC; ++ph) {
@@ -181,7 +181,7 @@ void attn_tlong_fwd_kernel(const float* __restrict__ qkv, const float* __restric
             const float* rkr = Ra + ps.tq * RST;
             const float* rqr = Rb + ps.tq * RST;
 #pragma unroll
-            for (int s = 0; s < TL_MAXT; ++s) {
+            for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
                 if (s < T) {
                     float a0 = 0.f, a1 = 0.f;
 #pragma unroll
@@ -203,7 +203,7 @@ void attn_tlong_fwd_kernel(const float* __restrict__ qkv, const float* __restric
         const float mt = mask ? mask[b * T + t] : 1.f;
         float mx = -INFINITY;
 #pragma unroll
-        for (int s = 0; s < TL_MAXT; ++s) {
+        for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
             float v = -INFINITY;
             if (s < T) {
                 v = logit[s];
@@ -218,18 +218,18 @@ void attn_tlong_fwd_kernel(const float* __restrict__ qkv, const float* __restric
         }
         float sum = 0.f;
 #pragma unroll
-        for (int s = 0; s < TL_MAXT; ++s) {
+        for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
             const float e = (logit[s] == -INFINITY) ? 0.f : __expf(logit[s] - mx);
             logit[s] = e;
             sum += e;
         }
         const float inv = 1.0f / sum;
 #pragma unroll
-        for (int s = 0; s < TL_MAXT; ++s) logit[s] *= inv;
+        for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) logit[s] *= inv;
         if (attn_out) {
             float* ar = attn_out + ((((size_t)b * P + p) * heads + h) * T + t) * T;
 #pragma unroll
-            for (int s = 0; s < TL_MAXT; ++s)
+            for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s)
                 if (s < T) ar[s] = logit[s];
         }
     }
@@ -246,7 +246,7 @@ void attn_tlong_fwd_kernel(const float* __restrict__ qkv, const float* __restric
 #pragma unroll
             for (int u = 0; u < TL_NQ; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < TL_MAXT; ++s) {
+            for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
                 if (s < T) {
                     float pr = logit[s];
                     asm volatile("" : "+v"(pr));     // no hoisted broadcast pairs (see attention.hip)
@@ -326,9 +326,9 @@ void attn_tlong_bwd_rows_kernel(const float* __restrict__ qkv, const float* __re
             if (sl.k_ok & (1u << i)) st4(KV + sl.k_l[i], (sl.k_in & (1u << i)) ? st.kv[i] : z);
     };
 
-    float pr[TL_MAXT], dp[TL_MAXT];
+    float pr[TEMPORAL_MAXT_LONG], dp[TEMPORAL_MAXT_LONG];
 #pragma unroll
-    for (int s = 0; s < TL_MAXT; ++s) {
+    for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
         pr[s] = 0.f;
         dp[s] = 0.f;
     }
@@ -349,7 +349,7 @@ void attn_tlong_bwd_rows_kernel(const float* __restrict__ qkv, const float* __re
             const float* rbr = Rb + ps.tq * RST;
             if (lg) {
 #pragma unroll
-                for (int s = 0; s < TL_MAXT; ++s) {
+                for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
                     if (s < T) {
                         float a0 = 0.f, a1 = 0.f;
 #pragma unroll
@@ -365,7 +365,7 @@ void attn_tlong_bwd_rows_kernel(const float* __restrict__ qkv, const float* __re
                 }
             } else {
 #pragma unroll
-                for (int s = 0; s < TL_MAXT; ++s) {
+                for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
                     if (s < T) {
                         float a0 = 0.f;
 #pragma unroll
@@ -383,7 +383,7 @@ void attn_tlong_bwd_rows_kernel(const float* __restrict__ qkv, const float* __re
             const float mt = mask ? mask[b * T + t] : 1.f;
             float mx = -INFINITY;
 #pragma unroll
-            for (int s = 0; s < TL_MAXT; ++s) {
+            for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
                 float v = -INFINITY;
                 if (s < T) {
                     v = pr[s];
@@ -398,26 +398,26 @@ void attn_tlong_bwd_rows_kernel(const float* __restrict__ qkv, const float* __re
             }
             float sum = 0.f;
 #pragma unroll
-            for (int s = 0; s < TL_MAXT; ++s) {
+            for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
                 const float e = (pr[s] == -INFINITY) ? 0.f : __expf(pr[s] - mx);
                 pr[s] = e;
                 sum += e;
             }
             const float inv = 1.0f / sum;
 #pragma unroll
-            for (int s = 0; s < TL_MAXT; ++s) pr[s] *= inv;
+            for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) pr[s] *= inv;
         }
     }
     // dS = P * (dP - sum_s P dP); rows of P and dS to the workspace
     if (active) {
         float dsum = 0.f;
 #pragma unroll
-        for (int s = 0; s < TL_MAXT; ++s) dsum += pr[s] * dp[s];
+        for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) dsum += pr[s] * dp[s];
         const size_t wid = ((size_t)b * P + p) * heads + h;
         float* prow = Pg + (wid * T + t) * T;
         float* srow = dSg + (wid * T + t) * T;
 #pragma unroll
-        for (int s = 0; s < TL_MAXT; ++s) {
+        for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
             dp[s] = pr[s] * (dp[s] - dsum);
             if (s < T) {
                 prow[s] = pr[s];
@@ -438,7 +438,7 @@ void attn_tlong_bwd_rows_kernel(const float* __restrict__ qkv, const float* __re
 #pragma unroll
             for (int u = 0; u < TL_NQ; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < TL_MAXT; ++s) {
+            for (int s = 0; s < TEMPORAL_MAXT_LONG; ++s) {
                 if (s < T) {
                     float w = dp[s];
                     asm volatile("" : "+v"(w));
@@ -479,13 +479,13 @@ void attn_tlong_bwd_cols_kernel(const float* __restrict__ qkv, const float* __re
     for (int i = 0; i < (TL_RB > TL_KB ? TL_RB : TL_KB); ++i) u4[i] = tl_u4(i);
 
     // column s of this pixel's P and dS matrices
-    float pc[TL_MAXT], dc[TL_MAXT];
+    float pc[TEMPORAL_MAXT_LONG], dc[TEMPORAL_MAXT_LONG];
     {
         const size_t wid = active ? ((size_t)b * P + p) * heads + h : 0;
         const float* pcol = Pg + wid * T * T + (active ? s : 0);
         const float* scol = dSg + wid * T * T + (active ? s : 0);
 #pragma unroll
-        for (int t = 0; t < TL_MAXT; ++t) {
+        for (int t = 0; t < TEMPORAL_MAXT_LONG; ++t) {
             pc[t] = (active && t < T) ? pcol[(size_t)t * T] : 0.f;
             dc[t] = (active && t < T) ? scol[(size_t)t * T] : 0.f;
         }
@@ -533,7 +533,7 @@ void attn_tlong_bwd_cols_kernel(const float* __restrict__ qkv, const float* __re
                 accV[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
-            for (int t = 0; t < TL_MAXT; ++t) {
+            for (int t = 0; t < TEMPORAL_MAXT_LONG; ++t) {
                 if (t < T) {
                     float wk = dc[t], wv = pc[t];
                     asm volatile("" : "+v"(wk), "+v"(wv));
@@ -570,37 +570,37 @@ dim3 tl_grid(const TLGeom& g, int B) {
 size_t tl_lds(int T) { return (size_t)(2 * TL_TG + TL_NPX) * (T * TL_FC + 4) * sizeof(float); }
 
 bool tl_covered(int T, int C, int heads) {
-    return T > 32 && T <= TL_MAXT && (C / heads) % TL_FC == 0;
+    return T > TEMPORAL_MAXT && T <= TEMPORAL_MAXT_LONG && (C / heads) % TL_FC == 0;
 }
 
 }  // namespace
 
-// Called by lfvdm_attn_temporal_ring / lfvdm_attn_temporal_bwd (attention.hip, attention_bwd.hip) for 33 <= T <= 64.
-int lfvdm_attn_temporal_long(const float* qkv, const float* Rq, const float* Rk, const float* Rv, const float* mask, float* o,
-                             float* attn_out, int B, int T, int P, int C, int heads, RSel rsel, hipStream_t s) {
-    if (!tl_covered(T, C, heads)) return LFVDM_E_UNSUPPORTED;
-    const TLGeom g = tl_geom(T, P, C, heads);
-    const size_t lds = tl_lds(T);
+// The long-window entries of attention_temporal.h: lfvdm_attn_temporal_ring (attention.hip) and lfvdm_attn_temporal_bwd
+// (attention_bwd.hip) come here for 33 <= T <= 64.
+int lfvdm_attn_temporal_long(const TemporalFwd& a) {
+    if (!tl_covered(a.T, a.C, a.heads)) return LFVDM_E_UNSUPPORTED;
+    const TLGeom g = tl_geom(a.T, a.P, a.C, a.heads);
+    const size_t lds = tl_lds(a.T);
     static DynLdsLimit limit;
     if (int rc = limit.ensure(reinterpret_cast<const void*>(&attn_tlong_fwd_kernel), lds)) return rc;
-    hipLaunchKernelGGL(attn_tlong_fwd_kernel, tl_grid(g, B), dim3(256), lds, s, qkv, Rq, Rk, Rv, mask, o, attn_out, rsel, g);
+    hipLaunchKernelGGL(attn_tlong_fwd_kernel, tl_grid(g, a.B), dim3(256), lds, a.s, a.qkv, a.Rq, a.Rk, a.Rv, a.mask, a.o, a.attn_out,
+                       a.rsel, g);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
 
-int lfvdm_attn_temporal_long_bwd(const float* qkv, const float* d_o, const float* Rq, const float* Rk, const float* Rv,
-                                 const float* mask, float* Pg, float* dSg, float* dqkv, int B, int T, int P, int C, int heads,
-                                 hipStream_t s) {
-    if (!tl_covered(T, C, heads)) return LFVDM_E_UNSUPPORTED;
-    const TLGeom g = tl_geom(T, P, C, heads);
-    const size_t lds = tl_lds(T);
+int lfvdm_attn_temporal_long_bwd(const TemporalBwd& a) {
+    if (!tl_covered(a.T, a.C, a.heads)) return LFVDM_E_UNSUPPORTED;
+    const TLGeom g = tl_geom(a.T, a.P, a.C, a.heads);
+    const size_t lds = tl_lds(a.T);
     static DynLdsLimit limit_rows, limit_cols;
     if (int rc = limit_rows.ensure(reinterpret_cast<const void*>(&attn_tlong_bwd_rows_kernel), lds)) return rc;
     if (int rc = limit_cols.ensure(reinterpret_cast<const void*>(&attn_tlong_bwd_cols_kernel), lds)) return rc;
-    const dim3 grid = tl_grid(g, B);
-    hipLaunchKernelGGL(attn_tlong_bwd_rows_kernel, grid, dim3(256), lds, s, qkv, d_o, Rq, Rk, Rv, mask, dqkv, Pg, dSg, g);
+    const dim3 grid = tl_grid(g, a.B);
+    hipLaunchKernelGGL(attn_tlong_bwd_rows_kernel, grid, dim3(256), lds, a.s, a.qkv, a.d_o, a.Rq, a.Rk, a.Rv, a.mask, a.dqkv, a.ws_p,
+                       a.ws_ds, g);
     LFVDM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(attn_tlong_bwd_cols_kernel, grid, dim3(256), lds, s, qkv, d_o, Rq, Pg, dSg, dqkv, g);
+    hipLaunchKernelGGL(attn_tlong_bwd_cols_kernel, grid, dim3(256), lds, a.s, a.qkv, a.d_o, a.Rq, a.ws_p, a.ws_ds, a.dqkv, g);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }
