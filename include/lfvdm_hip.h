@@ -619,6 +619,28 @@ int lfvdm_masked_mse(const float* a, const float* b, const float* mask, float* o
 int lfvdm_masked_mse_bwd(const float* target, const float* pred, const float* mask, const float* g, float* dpred, int B, int T,
                          int frame_inner, void* stream);
 
+/* Loss head of a timestep-weighted training step (GaussianDiffusion.set_loss_weighting: min-SNR-gamma, Hang et al. 2023; P2,
+ * Choi et al. 2022; a caller's table - no counterpart in the reference, whose MSE weights every timestep equally).  One pass
+ * over target / pred (each [B][T][frame_inner]) gives the three per-row terms of training_losses:
+ *   mse[b]      = lfvdm_masked_mse(target, pred, mask)[b]       BITWISE: the same thread-to-element mapping (16-byte loads
+ *   eval_mse[b] = lfvdm_masked_mse(target, pred, eval_mask)[b]  when frame_inner % 4 == 0, scalar loads otherwise), the same wave
+ *                                                               sums and the same order of the 16 wave partials
+ *   loss[b]     = mse[b] * wtab[clamp(t[b], 0, n_t - 1)]        one fp32 product of the final mse value
+ * mask / eval_mask are [B][T] or NULL (all ones); wtab holds n_t floats.  The weight is gathered by t[b] on the device because
+ * the training step is replayed as a captured graph whose t changes with every replay; the index is clamped, so no t reads
+ * outside the table.  No atomics: deterministic.  frame_inner % 4 == 0 with a target or pred that is not 16-byte aligned ->
+ * LFVDM_E_UNSUPPORTED (the 16-byte sweep is part of the summation order); a NULL required pointer or a non-positive size ->
+ * LFVDM_E_SHAPE.
+ * Python side: TrainLoop(loss_weighting=...) > args.loss_weighting > the environment's LFVDM_LOSS_WEIGHTING ("none",
+ * "min_snr[:gamma]", "p2[:k[:gamma]]") > "none"; with "none" neither entry is called. */
+int lfvdm_train_loss(const float* target, const float* pred, const float* mask, const float* eval_mask, const int64_t* t,
+                     const float* wtab, int n_t, float* mse, float* eval_mse, float* loss, int B, int T, int frame_inner,
+                     void* stream);
+/* Gradient of loss w.r.t. pred, one launch, every element written, no atomics:
+ * dpred = -2 (target - pred) * mask[b][frame] * wtab[clamp(t[b], 0, n_t - 1)] * g[b] / (T * frame_inner); mask may be NULL. */
+int lfvdm_train_loss_bwd(const float* target, const float* pred, const float* mask, const int64_t* t, const float* wtab, int n_t,
+                         const float* g, float* dpred, int B, int T, int frame_inner, void* stream);
+
 /* One term of the variational bound per batch row, in bits per dimension (_vb_terms_bpd, gaussian_diffusion.py:687-720
  * with losses.py:12-77), fixed sigma, one pass over x_start / x_t / model_out (each [B][T][frame_inner]):
  *   x0-hat     = LFVDM_MEAN_EPS: sqrt_recip_acp[t] x_t - sqrt_recipm1_acp[t] model_out | LFVDM_MEAN_X0: model_out,

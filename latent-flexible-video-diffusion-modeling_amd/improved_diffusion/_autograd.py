@@ -34,6 +34,36 @@ def masked_mse(target, pred, mask):
     return _MaskedMSE.apply(target, pred, mask)
 
 
+class _TrainLoss(th.autograd.Function):
+    """The loss head of a timestep-weighted training step in one launch (lfvdm_train_loss): (mse, eval_mse, loss) with
+    mse / eval_mse bitwise ``masked_mse`` under ``mask`` / ``eval_mask`` and loss[b] = mse[b] * wtab[t[b]], the weight gathered
+    on the device (``t`` changes under a captured graph).  Only ``loss`` is differentiable, with respect to ``pred``:
+    d/dpred = -2 (target - pred) * mask / inner * wtab[t[b]] * grad[b] (lfvdm_train_loss_bwd)."""
+
+    @staticmethod
+    def forward(ctx, target, pred, mask, eval_mask, t, wtab):
+        B, T = pred.shape[0], pred.shape[1]
+        target, pred = target.contiguous(), pred.contiguous()
+        t = t.to(th.int64).contiguous()
+        m, me = (None if k is None else k.reshape(B, T).to(th.float32).contiguous() for k in (mask, eval_mask))
+        mse, eval_mse, loss = (th.empty(B, device=pred.device, dtype=th.float32) for _ in range(3))
+        nat.train_loss(target, pred, m, me, t, wtab, mse, eval_mse, loss)
+        ctx.save_for_backward(target, pred, m, t, wtab)
+        ctx.mark_non_differentiable(mse, eval_mse)
+        return mse, eval_mse, loss
+
+    @staticmethod
+    def backward(ctx, _g_mse, _g_eval, g):
+        target, pred, m, t, wtab = ctx.saved_tensors
+        d = th.empty_like(pred)
+        nat.train_loss_bwd(target, pred, m, t, wtab, g.contiguous().float(), d)
+        return None, d, None, None, None, None
+
+
+def train_loss(target, pred, mask, eval_mask, t, wtab):
+    return _TrainLoss.apply(target, pred, mask, eval_mask, t, wtab)
+
+
 class _VbTerm(th.autograd.Function):
     """vb[b] of ``GaussianDiffusion._vb_terms_bpd`` with clip_denoised=False (reference gaussian_diffusion.py:687-720, the
     KL training loss): one HIP launch forward (lfvdm_vb_terms), one backward (lfvdm_vb_terms_bwd, the closed-form gradient);

@@ -185,6 +185,8 @@ _SIGS = {
     "lfvdm_adamw_ema_clip": ([C.POINTER(AdamWArgs), c_fp, c_fp], c_i),
     "lfvdm_q_sample": ([c_fp] * 6 + [c_i, c_i, c_fp], c_i),
     "lfvdm_masked_mse": ([c_fp] * 4 + [c_i, c_i, c_i, c_fp], c_i),
+    "lfvdm_train_loss": ([c_fp] * 6 + [c_i] + [c_fp] * 3 + [c_i, c_i, c_i, c_fp], c_i),
+    "lfvdm_train_loss_bwd": ([c_fp] * 5 + [c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_prepare_batch": ([c_fp] * 6 + [c_i] * 4 + [c_fp], c_i),
     "lfvdm_chain_plan": ([C.POINTER(ChainStage), c_i, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], c_i),
@@ -736,6 +738,21 @@ def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):
 
 def masked_mse(a, b, mask, out, B, T, frame_inner):
     check(lib().lfvdm_masked_mse(ptr(a), ptr(b), ptr(mask), ptr(out), B, T, frame_inner, stream()), "lfvdm_masked_mse")
+
+
+def train_loss(target, pred, mask, eval_mask, t, wtab, mse, eval_mse, loss):
+    """The weighted loss head in one launch (lfvdm_train_loss): mse / eval_mse (B,) as ``masked_mse`` gives them under ``mask`` /
+    ``eval_mask`` ((B, T) fp32 or None), loss = mse * wtab[t] with the index clamped into the table.  t: (B,) int64."""
+    B, T = pred.shape[0], pred.shape[1]
+    check(lib().lfvdm_train_loss(ptr(target), ptr(pred), ptr(mask), ptr(eval_mask), ptr(t, torch.int64), ptr(wtab), wtab.numel(),
+                                 ptr(mse), ptr(eval_mse), ptr(loss), B, T, pred.numel() // (B * T), stream()), "lfvdm_train_loss")
+
+
+def train_loss_bwd(target, pred, mask, t, wtab, g, dpred):
+    """dpred = g[b] * d loss[b] / d pred (lfvdm_train_loss_bwd); every element is written."""
+    B, T = pred.shape[0], pred.shape[1]
+    check(lib().lfvdm_train_loss_bwd(ptr(target), ptr(pred), ptr(mask), ptr(t, torch.int64), ptr(wtab), wtab.numel(), ptr(g),
+                                     ptr(dpred), B, T, pred.numel() // (B * T), stream()), "lfvdm_train_loss_bwd")
 
 
 def grad_norm_nparts(n):

@@ -29,7 +29,12 @@ What is native here
     reference :687-720, :743-753, :798-888, losses.py) with fixed sigma: the KL / discretized-decoder term of a batch row,
     its x0 and epsilon MSEs and its closed-form gradient are two HIP kernels (csrc/vb_terms.hip, ``_autograd._VbTerm``);
     ``calc_bpd_loop`` replays ONE captured hipGraph per evaluation step (clock, noise draw, q_sample, U-Net forward, term)
-    over a private plan (``BpdEvaluator``), like the samplers.
+    over a private plan (``BpdEvaluator``), like the samplers;
+  * timestep loss weighting (``set_loss_weighting``: Min-SNR-gamma, Hang et al. 2023; P2, Choi et al. 2022; a caller's table -
+    not in the reference): float64 tables from this diffusion's own ``alphas_cumprod``, and one HIP launch that reads target and
+    output once and returns mse, eval-mse and loss = w[t] * mse with the weight gathered by ``t`` on the device
+    (csrc/train_loss.hip, ``_autograd._TrainLoss``).  Off by default; its effect on this model's convergence or sample
+    quality has not been measured.
 
 Out of scope (not reached by the default CLIs): learned sigma (``learn_sigma=True``, also together with
 ``use_kl``: the reference's own 5-D code path asserts on it, so there is no behaviour to match),
@@ -91,6 +96,39 @@ def _bshape(t, ndim):
     return t.view(-1, *([1] * (ndim - 1)))
 
 
+LOSS_WEIGHTING_KINDS = ("none", "min_snr", "p2", "table")
+
+
+def _num(v):
+    """Shortest text that parses back to the float v ("5" for 5.0)."""
+    r = repr(float(v))
+    return r[:-2] if r.endswith(".0") else r
+
+
+def parse_loss_weighting(spec):
+    """"none", "min_snr[:gamma]" or "p2[:k[:gamma]]" -> the keyword arguments of ``GaussianDiffusion.set_loss_weighting``
+    (what LFVDM_LOSS_WEIGHTING and ``args.loss_weighting`` hold; a dict of those arguments passes through, which is how a
+    "table" is given).  Only the shape of the string is judged here - the setter validates the values.  ValueError otherwise."""
+    if isinstance(spec, dict):
+        return dict(spec)
+    if not isinstance(spec, str):
+        raise ValueError(f"loss weighting must be a string such as 'min_snr:5' or a dict of set_loss_weighting arguments, got {spec!r}")
+    kind, *rest = [s.strip() for s in spec.strip().split(":")]
+    names = {"none": (), "min_snr": ("gamma",), "p2": ("k", "gamma")}.get(kind)
+    if names is None:
+        raise ValueError(f"unknown loss weighting {spec!r}: 'none', 'min_snr[:gamma]' or 'p2[:k[:gamma]]' "
+                         "(a 'table' is passed as a dict with its array)")
+    if len(rest) > len(names):
+        raise ValueError(f"loss weighting {spec!r}: {kind!r} takes at most {len(names)} number(s)")
+    kw = {"kind": kind}
+    for name, text in zip(names, rest):
+        try:
+            kw[name] = float(text)
+        except ValueError:
+            raise ValueError(f"loss weighting {spec!r}: {name} must be a number, got {text!r}") from None
+    return kw
+
+
 class GaussianDiffusion:
     """Training / sampling utilities (reference :101-181).  Same constructor and attributes."""
 
@@ -132,6 +170,7 @@ class GaussianDiffusion:
         self._ddim_cache = {}
         self._samplers = {}
         self._bpd_evals = {}
+        self.set_loss_weighting("none")
         self.setup_enc_dec()
 
     # ------------------------------------------------------------------ tables on device
@@ -237,6 +276,91 @@ class GaussianDiffusion:
             tb = {"k1": dd["k1"], "k2": dd["k2"],
                   "k3": th.from_numpy(self.dpm_solver_coefficients()["k3"]).float().to(device)}
             self._ddim_cache[key] = tb
+        return tb
+
+    # ------------------------------------------------------------------ timestep loss weighting (not in the reference)
+    def set_loss_weighting(self, kind="none", *, gamma=None, k=None, table=None):
+        """Per-timestep weight w[t] of the MSE training loss: ``training_losses`` returns loss = w[t] * mse (mse and eval-mse
+        stay unweighted).  With snr[t] = alphas_cumprod[t] / (1 - alphas_cumprod[t]) of THIS diffusion (a SpacedDiffusion: of
+        its respaced steps), in float64:
+
+          "none"     1 - the default; ``training_losses`` is then exactly the unweighted code path
+          "min_snr"  Min-SNR-gamma (Hang et al. 2023), gamma > 0, default 5:
+                       epsilon prediction min(snr, gamma) / snr (1 where snr == 0), x0 prediction min(snr, gamma)
+          "p2"       P2 (Choi et al. 2022), k > 0 default 1, gamma >= 0 default 1:
+                       epsilon prediction (k + snr)^-gamma, x0 prediction snr (k + snr)^-gamma
+          "table"    ``table``: num_timesteps values, finite, >= 0, representable in float32; the same for both mean types
+
+        The x0 weight of "min_snr" and "p2" is snr times the epsilon weight, so both mean types optimise one objective.
+        ValueError: an unknown kind, an argument the kind does not take, a gamma or k outside its range, a bad table, or any
+        kind but "none" with a KL loss type (the bound has its own weighting)."""
+        if kind not in LOSS_WEIGHTING_KINDS:
+            raise ValueError(f"unknown loss weighting kind {kind!r}: one of {LOSS_WEIGHTING_KINDS}")
+        takes = {"none": (), "min_snr": ("gamma",), "p2": ("k", "gamma"), "table": ("table",)}[kind]
+        given = {"gamma": gamma, "k": k, "table": table}
+        for name, v in given.items():
+            if v is not None and name not in takes:
+                raise ValueError(f"loss weighting {kind!r} takes no {name!r}")
+        if kind != "none" and self.loss_type.is_vb():
+            raise ValueError(f"loss weighting {kind!r} applies to the MSE losses: {self.loss_type} has the bound's own weighting")
+
+        def number(name, default, zero_ok=False):
+            v = given[name]
+            try:
+                v = float(default if v is None else v)
+            except (TypeError, ValueError):
+                raise ValueError(f"loss weighting {kind!r}: {name} must be a number, got {given[name]!r}") from None
+            if not math.isfinite(v) or v < 0 or (v == 0 and not zero_ok):
+                raise ValueError(f"loss weighting {kind!r}: {name} must be finite and {'>=' if zero_ok else '>'} 0, got {v!r}")
+            return v
+
+        n = self.num_timesteps
+        acp = self.alphas_cumprod
+        snr = acp / (1.0 - acp)
+        x0 = self.predicts_xstart
+        if kind == "none":
+            w, spec = np.ones(n, dtype=np.float64), "none"
+        elif kind == "min_snr":
+            g = number("gamma", 5.0)
+            capped = np.minimum(snr, g)
+            w = capped if x0 else np.where(snr > 0, capped / np.where(snr > 0, snr, 1.0), 1.0)
+            spec = f"min_snr:{_num(g)}"
+        elif kind == "p2":
+            kk, g = number("k", 1.0), number("gamma", 1.0, zero_ok=True)
+            w = (kk + snr) ** -g
+            w = snr * w if x0 else w
+            spec = f"p2:{_num(kk)}:{_num(g)}"
+        else:
+            if table is None:
+                raise ValueError("loss weighting 'table' needs table=<num_timesteps weights>")
+            try:
+                w = np.array(table, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("loss weighting 'table': the table must be an array of numbers") from None
+            if w.shape != (n,):
+                raise ValueError(f"loss weighting 'table': expected {n} weights (num_timesteps), got shape {w.shape}")
+            spec = "table"
+        with np.errstate(over="ignore"):
+            ok = np.isfinite(w).all() and (w >= 0).all() and np.isfinite(w.astype(np.float32)).all()
+        if not ok:
+            raise ValueError(f"loss weighting {kind!r}: every weight must be finite, >= 0 and representable in float32")
+        self._loss_weighting, self._loss_weights, self._loss_weight_cache = spec, w, {}
+
+    @property
+    def loss_weighting(self):
+        """The weighting in force as ``parse_loss_weighting`` reads it ("none", "min_snr:5", "p2:1:1"), or "table"."""
+        return self._loss_weighting
+
+    def loss_weights(self):
+        """The float64 weight table w[t] of ``set_loss_weighting`` (a copy)."""
+        return self._loss_weights.copy()
+
+    def loss_weight_table(self, device):
+        """fp32 device copy of ``loss_weights``, uploaded once per device and weighting."""
+        key = str(device)
+        tb = self._loss_weight_cache.get(key)
+        if tb is None:
+            tb = self._loss_weight_cache[key] = th.from_numpy(self._loss_weights).float().to(device)
         return tb
 
     def _gather(self, name, t, ndim):
@@ -616,7 +740,10 @@ class GaussianDiffusion:
 
         KL losses (``use_kl=True``: LossType.RESCALED_KL, or LossType.KL; reference :743-753): {'loss'} alone, the
         variational-bound term of ``t`` with clip_denoised=False over ALL frames (the masks are not used), times
-        num_timesteps for RESCALED_KL; the gradient reaches the network through ``_autograd._VbTerm``."""
+        num_timesteps for RESCALED_KL; the gradient reaches the network through ``_autograd._VbTerm``.
+
+        ``set_loss_weighting`` other than "none" (MSE losses): 'loss' = w[t] * mse, a tensor of its own and the only
+        differentiable term; 'mse' and 'eval-mse' keep their unweighted values (one launch, ``_autograd._TrainLoss``)."""
         self._check_native_modes()
         if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE, LossType.KL, LossType.RESCALED_KL):
             raise NotImplementedError(self.loss_type)
@@ -635,6 +762,12 @@ class GaussianDiffusion:
         # (model_kwargs["x0"] is the window's conditioning frames - an INPUT of the network in either mode; the regression
         # target of an x0-prediction model is x_start, the clean latents of all frames)
         target = x_start if self.predicts_xstart else noise
+        if self._loss_weighting != "none":
+            # one launch for the three terms; the weight is gathered by t ON THE DEVICE (t changes under TrainLoop's captured
+            # micro-step).  mse / eval-mse are bitwise the unweighted path's; the gradient flows through "loss" alone
+            from ._autograd import train_loss
+            mse, eval_mse, loss = train_loss(target, model_output, latent_mask, eval_mask, t, self.loss_weight_table(x_start.device))
+            return {"mse": mse, "eval-mse": eval_mse, "loss": loss}
         terms = {"mse": masked_mse(target, model_output, latent_mask)}
         with th.no_grad():
             terms["eval-mse"] = masked_mse(target, model_output.detach(), eval_mask)

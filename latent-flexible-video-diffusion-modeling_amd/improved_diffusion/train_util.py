@@ -58,6 +58,20 @@ def resolve_max_grad_norm(keyword=None, args=None):
     return value
 
 
+def resolve_loss_weighting(keyword=None, args=None):
+    """Timestep loss weighting of ``TrainLoop``, resolved as ``max_grad_norm`` is: the ``loss_weighting`` keyword, else
+    ``args.loss_weighting``, else the environment's LFVDM_LOSS_WEIGHTING, else "none" -> the keyword arguments of
+    ``GaussianDiffusion.set_loss_weighting``.  A value is a string ("none", "min_snr[:gamma]", "p2[:k[:gamma]]") or a dict of
+    those arguments (a "table").  Malformed: ValueError."""
+    from .gaussian_diffusion import parse_loss_weighting
+    value = keyword
+    if value is None:
+        value = getattr(args, "loss_weighting", None)
+    if value is None:
+        value = os.environ.get("LFVDM_LOSS_WEIGHTING") or None
+    return parse_loss_weighting("none" if value is None else value)
+
+
 class ParamArena:
     """Flat fp32 storage for a list of parameters: ``p.data`` and ``p.grad`` become views of two
     contiguous buffers, which gives one collective per bucket, one fused optimizer launch and a memset for
@@ -105,11 +119,13 @@ class TrainLoop:
     def __init__(self, *, model, diffusion, data, batch_size, microbatch, lr, ema_rate, log_interval, save_interval,
                  resume_checkpoint, use_fp16, diffusion_space_kwargs, fp16_scale_growth, schedule_sampler, weight_decay,
                  lr_anneal_steps, sample_interval, pad_with_random_frames, max_frames, enc_dec_chunk_size, args,
-                 max_grad_norm=None):
+                 max_grad_norm=None, loss_weighting=None):
         if use_fp16:
             raise NotImplementedError("use_fp16 is off in the reference defaults; the native path is fp32")
         self.args = args
         self.max_grad_norm = resolve_max_grad_norm(max_grad_norm, args)     # 0: no clipping, no non-finite skip
+        diffusion.set_loss_weighting(**resolve_loss_weighting(loss_weighting, args))     # validated here; "none": today's path
+        self.loss_weighting = diffusion.loss_weighting
         dist_util.limit_host_threads()
         self.model = model
         self.diffusion = diffusion
