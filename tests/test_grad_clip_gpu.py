@@ -1,6 +1,7 @@
 """Global-norm gradient clipping and the non-finite step skip on the MI355X (csrc/grad_clip.hip): the norm launches against
 numpy fp64, the clip coefficient and the clipped fused AdamW/EMA launch against torch in fp64, the skip on an inf / NaN
-gradient, ``TrainLoop`` with ``max_grad_norm`` (on: against the loop's host-memory arithmetic; off: bitwise the loop
+gradient, every EMA-count instance and both loop shapes of the capped grid of the fused kernel (plain and clipping entry,
+``grad_sqsum`` included) against fp64, ``TrainLoop`` with ``max_grad_norm`` (on: against the loop's host-memory arithmetic; off: bitwise the loop
 without the keyword and none of the new entries called) and two ranks agreeing bitwise.  GPU only."""
 import argparse
 import ctypes
@@ -73,7 +74,7 @@ def test_norm_matches_fp64(n, offset):
 
 
 class _Opt:
-    """p / g / m / v and two EMA copies of n floats on the device + the launch arguments of one optimizer step."""
+    """p / g / m / v and n_ema (two unless told) EMA copies of n floats on the device + the launch arguments of one optimizer step."""
 
     def __init__(self, n, seed=0, n_ema=2):
         gen = torch.Generator().manual_seed(seed)
@@ -82,7 +83,7 @@ class _Opt:
         self.g = (torch.randn(n, generator=gen) * 0.1).cuda()
         self.m = torch.zeros(n, device="cuda")
         self.v = torch.zeros(n, device="cuda")
-        self.rates = [0.9, 0.999][:n_ema]
+        self.rates = [0.9, 0.999, 0.99, 0.9999][:n_ema]
         self.ema = [self.p.clone() for _ in self.rates]
         self.lr, self.betas, self.eps, self.wd, self.scale = 1e-3, (0.9, 0.999), 1e-8, 0.01, 0.5
 
@@ -191,6 +192,85 @@ def test_nonfinite_gradient_skips_the_step():
     for x, y in zip(ref.state(), o.state()):
         assert torch.equal(x, y)
     assert not torch.equal(o.p, before[0])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# every instance and every grid shape of adamw_ema_kernel (csrc/adamw_ema_body.h)
+# ------------------------------------------------------------------------------------------------------------------------
+GRID_CAP = 2048 * 256                       # float4 slots of one pass of the capped grid
+N_SECOND_SLOT = 4 * (GRID_CAP + 100) + 2    # one loop pass; the u = 1 slot is valid for 100 threads only; a 2-element tail
+N_SECOND_PASS = 4 * (2 * GRID_CAP + 257) + 1  # a second loop pass (257 threads) whose u = 1 slot is invalid everywhere; 1-element tail
+
+
+def _sqsum_adds(n):
+    """Additions along the longest path of the plain entry's grad_sqsum: 8 per loop pass of a thread (two float4 slots of
+    four squares), 1 for the tail element, 6 shuffle steps, 3 across the waves, one float atomic per workgroup."""
+    blocks = min(2048, max(1, (n // 4 + 255) // 256))
+    passes = max(1, math.ceil((n // 4) / (2 * 256 * blocks)))
+    return 8 * passes + 1 + 6 + 3 + blocks, blocks, passes
+
+
+def _steps_against_fp64(o, entry):
+    """Two steps of the plain or the clipping entry (the second on non-zero moments) against fp64 torch.optim.AdamW (+
+    clip_grad_norm_) + EMA, vectorised on the CPU: atol 1e-6 / rtol 1e-5 as test_clipped_step_matches_fp64_torch.  Plain
+    entry: grad_sqsum against fp64 as well.  Its terms are non-negative, so its relative error is at most (additions
+    along the longest path) * 2^-24, counted by _sqsum_adds from n."""
+    from improved_diffusion import _native as nat
+    ref = torch.nn.Parameter(o.p.double().cpu())
+    ref_ema = [ref.detach().clone() for _ in o.rates]
+    opt = torch.optim.AdamW([ref], lr=o.lr, betas=o.betas, eps=o.eps, weight_decay=o.wd)
+    stat, sqsum = torch.zeros(4, device="cuda"), torch.zeros(1, device="cuda")
+    gen = torch.Generator().manual_seed(o.n % 9973)
+    for step in (1, 2):
+        o.g.copy_(torch.randn(o.n, generator=gen) * (0.1 * step))
+        ref.grad = o.g.double().cpu() * o.scale
+        if entry == "clip":
+            max_norm = 0.1 * float(ref.grad.norm())
+            torch.nn.utils.clip_grad_norm_([ref], max_norm, error_if_nonfinite=False)
+            o.step_clip(step, max_norm, stat)
+            assert 0.0 < float(stat[1]) < 1.0 and _ints(stat) == [0, 0]
+        else:
+            want = float((ref.grad * ref.grad).sum())
+            a = o.args(step)
+            sqsum.zero_()
+            a.grad_sqsum = sqsum.data_ptr()
+            nat.check(nat.lib().lfvdm_adamw_ema(ctypes.byref(a), nat.stream()), "lfvdm_adamw_ema")
+            torch.cuda.synchronize()
+            adds, blocks, passes = _sqsum_adds(o.n)
+            rel = abs(float(sqsum[0]) - want) / want
+            print(f"[adamw sqsum] n={o.n} n_ema={len(o.rates)} step={step} blocks={blocks} passes={passes} rel.err={rel:.3e} "
+                  f"bound={adds * 2.0 ** -24:.3e}")
+            assert rel <= adds * 2.0 ** -24
+        opt.step()
+        for e, r in zip(ref_ema, o.rates):
+            e.mul_(r).add_(ref.detach(), alpha=1.0 - r)
+        pairs = [("p", o.p, ref.detach()), ("m", o.m, opt.state[ref]["exp_avg"]), ("v", o.v, opt.state[ref]["exp_avg_sq"])]
+        pairs += [(f"ema{k}", e, re_) for k, (e, re_) in enumerate(zip(o.ema, ref_ema))]
+        for name, got, want_t in pairs:
+            assert torch.allclose(got.cpu(), want_t.float(), atol=1e-6, rtol=1e-5), (name, step)
+
+
+@pytest.mark.parametrize("n_ema", [0, 1, 2, 3, 4])
+def test_every_ema_count_matches_fp64_torch(n_ema):
+    """The five NE instances of the plain entry (0..4 EMA copies, each with its own rate) at n = 5003."""
+    o = _Opt(N_OPT, seed=10 + n_ema, n_ema=n_ema)
+    assert len(o.ema) == n_ema and len(set(o.rates)) == n_ema
+    _steps_against_fp64(o, "plain")
+
+
+@pytest.mark.parametrize("entry", ["plain", "clip"])
+@pytest.mark.parametrize("n", [N_SECOND_SLOT, N_SECOND_PASS], ids=["second_slot_100_threads", "second_pass_257_threads"])
+def test_capped_grid_passes_match_fp64_torch(n, entry):
+    """n beyond one float4 per thread of the capped 2048 x 256 grid: the clamped duplicate loads of the u = 1 slot (valid
+    for 100 threads, or for none in a second loop pass of 257 threads) and the scalar tail, in both entries, one EMA copy."""
+    n4 = n // 4
+    _, blocks, passes = _sqsum_adds(n)
+    assert blocks == 2048 and n % 4 != 0
+    if n == N_SECOND_SLOT:
+        assert passes == 1 and n4 - GRID_CAP == 100
+    else:
+        assert passes == 2 and n4 - 2 * GRID_CAP == 257
+    _steps_against_fp64(_Opt(n, seed=20, n_ema=1), entry)
 
 
 def _device_loop(cfg, sd, data_seed=0, **kw):
