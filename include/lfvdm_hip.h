@@ -600,6 +600,28 @@ int lfvdm_conv_out_update_ms_x0(const float* act, const float* Wp, const float* 
                                 const float* hist, const int64_t* t, const float* sqrt_recip_acp, const float* sqrt_recipm1_acp,
                                 const float* k1, const float* k2, const float* k3, int mean_type, int clip, float* sample,
                                 float* pred_xstart, int B, int T, int H, int W, int C, int Cout, void* stream);
+/* Known-region sampling (replacement conditioning as in RePaint, Lugmayr et al. 2022; not in the reference): the part of
+ * the video the caller knows is put back into the sampler's state after every step, at the step's noise level.
+ *   lfvdm_known_blend   in place over x (B, T, C, H, W), HW = H * W, with j = t[b] the timestep the step just consumed:
+ *                           x = m (sqrt_acp_prev[j] known + sqrt_1macp_prev[j] eps) + (1 - m) x
+ *                       m = mask[b][t][h][w] in [0, 1], a (B, T, H, W) tensor broadcast over the channels; where m is 0 the
+ *                       element keeps its bits, where m is 1 it is the bracket alone.  The tables are sqrt(alphas_cumprod_prev)
+ *                       and sqrt(1 - alphas_cumprod_prev): entry 0 is (1, 0), so after the last step the masked part IS known.
+ *                       eps != NULL: fixed noise, read from eps (B, T, C, H, W); seed and noise_out are not touched.
+ *                       eps == NULL: fresh noise, drawn in the kernel with the Philox construction of lfvdm_update_rng_x0
+ *                       - key seed[0] (required), counter (element quad, batch row, j, 1) - and stored to noise_out if given.
+ *   lfvdm_renoise       one forward diffusion step in place over x (B, inner), for resampling:
+ *                           x = sqrt_1mbeta[j] x + sqrt_beta[j] eps
+ *                       eps always fresh: key seed[0], counter (element quad, batch row, j, 2); noise_out optional.
+ * The fourth counter word is 0 in the update entries above, 1 in the blend and 2 in the re-noise: under one seed the three
+ * launches of a step draw from disjoint streams.  A missing required pointer, a non-positive size, B > 65535 or a per-row
+ * element count (T*C*HW, inner) that is not a multiple of 4 -> LFVDM_E_SHAPE, before anything is launched.  t[b] must index
+ * the tables (it is not checked, as in the update entries). */
+int lfvdm_known_blend(float* x, const float* known, const float* mask, const float* eps, float* noise_out, const int64_t* t,
+                      const float* sqrt_acp_prev, const float* sqrt_1macp_prev, const int64_t* seed, int B, int T, int C,
+                      int HW, void* stream);
+int lfvdm_renoise(float* x, float* noise_out, const int64_t* t, const float* sqrt_1mbeta, const float* sqrt_beta,
+                  const int64_t* seed, int B, int inner, void* stream);
 /* Sampler clock of the captured denoising step (the loop `for i in indices: t = th.tensor([i]*B)` of
  * gaussian_diffusion.py:509-512 and _WrappedModel's timestep map, respace.py:117-122, kept on the device):
  * t[b] <- max(t[b] - 1, 0);  model_t[b] <- model_timestep_table[t[b]]. */

@@ -1,6 +1,7 @@
 // Elementwise Gaussian-diffusion step math (gaussian_diffusion.py:200-218, 290-346, 369-401,
 // 787-788).  HBM-bound streaming kernels: float4 accesses, one table gather per batch row.
 #include "common_hip.h"
+#include "philox_normal.h"
 
 namespace {
 
@@ -123,35 +124,8 @@ __global__ __launch_bounds__(256) void p_sample_kernel(const float* x, const flo
     }
 }
 
-// ---- the same update with the Gaussian noise drawn in the kernel (one launch less per sampling step).
-// Counter-based: Philox4x32-10 (Salmon et al., SC'11) keyed by the chain's 64-bit seed, counter = (quad index within the
-// row, batch row, timestep, 0) -> four uniform words -> two Box-Muller pairs = the noise of four consecutive elements.
-// A given (seed, timestep, element) always gets the same value, whatever the launch geometry.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ f32x4 normal4(unsigned quad, unsigned row, unsigned step, unsigned k0, unsigned k1) {
-    unsigned r[4];
-    philox4x32_10(quad, row, step, 0u, k0, k1, r);
-    const float two_pi = 6.283185307179586f, s32 = 2.3283064365386963e-10f;      // 2^-32
-    const float u0 = ((float)r[0] + 1.0f) * s32, u1 = (float)r[1] * s32;         // u0 in (0, 1]
-    const float u2 = ((float)r[2] + 1.0f) * s32, u3 = (float)r[3] * s32;
-    const float m0 = sqrtf(-2.0f * logf(u0)), m1 = sqrtf(-2.0f * logf(u2));
-    float s0, c0, s1, c1;
-    sincosf(two_pi * u1, &s0, &c0);
-    sincosf(two_pi * u3, &s1, &c1);
-    return (f32x4){m0 * c0, m0 * s0, m1 * c1, m1 * s1};
-}
-
+// ---- the same update with the Gaussian noise drawn in the kernel (one launch less per sampling step): normal4 of
+// philox_normal.h, counter = (quad index within the row, batch row, timestep, NOISE_STREAM_UPDATE).
 template <int RULE, int MEAN>
 __global__ __launch_bounds__(256) void p_sample_rng_kernel(const float* x, const float* __restrict__ eps,
                                                            float* __restrict__ noise_out, const int64_t* __restrict__ t,

@@ -134,6 +134,8 @@ _SIGS = {
     "lfvdm_conv_out_update_x0": ([c_fp] * 13 + [c_i, c_i, c_i] + [c_fp] * 3 + [c_i] * 6 + [c_fp, c_fp], c_i),
     "lfvdm_update_ms_x0": ([c_fp] * 9 + [c_i, c_i] + [c_fp] * 2 + [c_i, c_i, c_fp], c_i),
     "lfvdm_conv_out_update_ms_x0": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 2 + [c_i] * 6 + [c_fp], c_i),
+    "lfvdm_known_blend": ([c_fp] * 9 + [c_i] * 4 + [c_fp], c_i),
+    "lfvdm_renoise": ([c_fp] * 6 + [c_i, c_i, c_fp], c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_vb_terms": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 4 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_vb_terms_bwd": ([c_fp] * 11 + [c_i, c_i, c_fp, c_i, c_i, c_i, c_fp], c_i),
@@ -705,6 +707,25 @@ def conv_out_update_ms_x0(act, wp, bias, out, x, hist, t, recip, recipm1, k1, k2
                                             ptr(recip), ptr(recipm1), ptr(k1), ptr(k2), ptr(k3), int(mean_type), int(bool(clip)),
                                             ptr(sample), ptr(pred), B, T, H, W, act.shape[-1], Cout, stream()),
           "lfvdm_conv_out_update_ms_x0")
+
+
+def known_blend(x, known, mask, t, a, s, eps=None, seed=None, noise_out=None):
+    """The known-region blend in place over ``x`` (B, T, C, H, W) (lfvdm_known_blend): ``mask`` (B, T, H, W) in [0, 1],
+    ``t`` the timestep the step just consumed, ``a`` / ``s`` the tables of ``GaussianDiffusion.known_region_tables``.
+    ``eps`` given: fixed noise; else fresh noise keyed by the device int64 ``seed``, stored to ``noise_out`` if given."""
+    B, T, Cx, H, W = x.shape
+    if known.shape != x.shape or tuple(mask.shape) != (B, T, H, W) or (eps is not None and eps.shape != x.shape):
+        raise RuntimeError("known_blend: known / eps are shaped like x (B, T, C, H, W) and mask is (B, T, H, W)")
+    check(lib().lfvdm_known_blend(ptr(x), ptr(known), ptr(mask), ptr(eps), ptr(noise_out), ptr(t, torch.int64), ptr(a), ptr(s),
+                                  ptr(seed, torch.int64) if seed is not None else None, B, T, Cx, H * W, stream()),
+          "lfvdm_known_blend")
+
+
+def renoise(x, t, c, d, seed, noise_out=None):
+    """One forward diffusion step in place (lfvdm_renoise): x = c[t] x + d[t] eps with fresh noise keyed by ``seed``."""
+    B = x.shape[0]
+    check(lib().lfvdm_renoise(ptr(x), ptr(noise_out), ptr(t, torch.int64), ptr(c), ptr(d), ptr(seed, torch.int64), B,
+                              x.numel() // B, stream()), "lfvdm_renoise")
 
 
 def vb_terms(x_start, x_t, out, noise, t, recip, recipm1, c1, c2, post_logvar, model_logvar, mask, mean_type, clip, vb,

@@ -169,6 +169,7 @@ class GaussianDiffusion:
         self._dev_cache = {}
         self._ddim_cache = {}
         self._samplers = {}
+        self._known_samplers = {}      # the known-region samplers: their step ends with one more launch (other graphs)
         self._bpd_evals = {}
         self.set_loss_weighting("none")
         self.setup_enc_dec()
@@ -275,6 +276,22 @@ class GaussianDiffusion:
             dd = self.ddim_tables(device, 0.0)
             tb = {"k1": dd["k1"], "k2": dd["k2"],
                   "k3": th.from_numpy(self.dpm_solver_coefficients()["k3"]).float().to(device)}
+            self._ddim_cache[key] = tb
+        return tb
+
+    def known_region_coefficients(self):
+        """float64 per-timestep tables of known-region sampling: ``a`` = sqrt(abar_prev) and ``s`` = sqrt(1 - abar_prev),
+        the level the state is at AFTER the step that consumed timestep t (a[0] = 1, s[0] = 0: after the last step the
+        known part is the clean known video), and ``sqrt_1mbeta`` / ``sqrt_beta``, one forward step back up to level t."""
+        return {"a": np.sqrt(self.alphas_cumprod_prev), "s": np.sqrt(1.0 - self.alphas_cumprod_prev),
+                "sqrt_1mbeta": np.sqrt(1.0 - self.betas), "sqrt_beta": np.sqrt(self.betas)}
+
+    def known_region_tables(self, device):
+        """fp32 device copies of ``known_region_coefficients``, uploaded once per device."""
+        key = ("known_region", str(device))
+        tb = self._ddim_cache.get(key)
+        if tb is None:
+            tb = {n: th.from_numpy(v).float().to(device) for n, v in self.known_region_coefficients().items()}
             self._ddim_cache[key] = tb
         return tb
 
@@ -724,6 +741,201 @@ class GaussianDiffusion:
         self._samplers[key] = s
         return s
 
+    # ------------------------------------------------------------------ known-region sampling (RePaint; not in the reference)
+    _KNOWN_RULES = {"ancestral": lambda eta: ("ancestral",), "ddim": lambda eta: ("ddim", float(eta)),
+                    "dpm_solver": lambda eta: ("dpmpp2m",)}
+    # resampling: repeat k of a timestep runs under the key seed + k * this modulo 2^64, so that its update, blend and
+    # re-noise draws differ from every other repeat's at the same (timestep, element); the stride is odd, so the keys of
+    # one timestep are distinct for every k below 2^64
+    _REPEAT_SEED_STRIDE = 0x1E3779B97F4A7C15
+
+    @classmethod
+    def _repeat_seed_offset(cls, k):
+        """k * stride reduced into the signed 64-bit range: what the device's wrapping int64 add takes as a scalar (the
+        Python product itself does not wrap, and torch refuses a scalar beyond 64 bits)."""
+        return ((int(k) * cls._REPEAT_SEED_STRIDE + 2 ** 63) % 2 ** 64) - 2 ** 63
+
+    def _known_region_sampler(self, unet, shape, clip_denoised, rule, fixed_noise):
+        """``_graph_sampler``'s twin for samplers whose captured step ends with the blend launch.  They live in a cache of
+        their own: the plain samplers, their graphs and their launch counts are what they were."""
+        key = (id(unet), shape, bool(clip_denoised), tuple(rule), "known")
+        s = self._known_samplers.pop(key, None)
+        if s is None or s.unet is not unet or s.engine is not unet.native_engine():
+            s = GraphSampler(self, unet, shape, clip_denoised, rule=rule)
+            s.enable_known_region(fixed_noise)
+            while len(self._known_samplers) >= 4:      # graphs pin device memory, as in _graph_sampler
+                self._known_samplers.pop(next(iter(self._known_samplers)))
+        self._known_samplers[key] = s
+        return s
+
+    @staticmethod
+    def _fork_generator(device):
+        """A private generator whose seed is a hash of the STATE of torch's generator for ``device``: ``th.manual_seed``
+        still fixes what it gives and torch's own generator is not advanced - what the chain draws from it is exactly what
+        the plain loop draws.  Two chains in a row get different streams because the first one advanced torch's generator
+        (its start noise, its seed); where nothing does - ``noise=`` given on the CPU slow path under a deterministic
+        rule - two chains in a row get the SAME fixed eps, as two calls behind the same ``th.manual_seed`` do."""
+        import hashlib
+        dev = th.device(device)
+        state = th.cuda.get_rng_state(dev) if dev.type == "cuda" else th.get_rng_state()
+        g = th.Generator(device=dev)
+        g.manual_seed(int.from_bytes(hashlib.sha256(state.numpy().tobytes()).digest()[:8], "little") >> 1)
+        return g
+
+    def _known_region_check(self, shape, known, known_mask, sampler, eta, resample_steps, noise, latent_mask):
+        """Every refusal of the known-region loops, before anything runs -> (rule, fixed_noise, repeats)."""
+        if sampler not in self._KNOWN_RULES:
+            raise ValueError(f"unknown sampler {sampler!r}: one of {sorted(self._KNOWN_RULES)}")
+        rule = self._KNOWN_RULES[sampler](eta)
+        if isinstance(resample_steps, bool) or int(resample_steps) != resample_steps or resample_steps < 1:
+            raise ValueError(f"resample_steps is a whole number >= 1, got {resample_steps!r}")
+        if resample_steps > 1 and sampler != "ancestral":
+            raise ValueError("resample_steps > 1 re-noises the state between repeats of a step: that is the ancestral "
+                             f"sampler's; {sampler!r} takes resample_steps=1")
+        if len(shape) != 5:
+            raise ValueError(f"shape is (B, T, C, H, W), got {tuple(shape)}")
+        B, T, _, H, W = shape
+        if tuple(known.shape) != tuple(shape):
+            raise ValueError(f"known has the shape of the sample {tuple(shape)}, got {tuple(known.shape)}")
+        try:
+            th.broadcast_shapes(tuple(known_mask.shape), (B, T, H, W))
+            ok = known_mask.dim() <= 4
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"known_mask broadcasts to (B, T, H, W) = {(B, T, H, W)}, got {tuple(known_mask.shape)}")
+        if noise is not None and tuple(noise.shape) != tuple(shape):
+            raise ValueError(f"noise has the shape of the sample {tuple(shape)}, got {tuple(noise.shape)}")
+        if latent_mask is not None and latent_mask.numel() != B * T:
+            raise ValueError(f"latent_mask holds one value per frame (B, T) = {(B, T)}, got {tuple(latent_mask.shape)}")
+        if not bool(((known_mask >= 0) & (known_mask <= 1)).all()):
+            raise ValueError("known_mask values lie in [0, 1]")
+        if not bool(th.isfinite(known).all()):
+            raise ValueError("known holds non-finite values")
+        return rule, rule[0] == "dpmpp2m" or (rule[0] == "ddim" and rule[1] == 0.0), int(resample_steps)
+
+    def known_region_sample_loop(self, model, shape, known, known_mask, *, sampler="ancestral", eta=0.0, resample_steps=1,
+                                 noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None, latent_mask=None,
+                                 device=None, progress=False, return_decoded=True):
+        """A full sampling chain in which part of the video is KNOWN: replacement conditioning as in RePaint (Lugmayr et al.
+        2022).  After every step the state becomes  m (a[t] known + s[t] eps) + (1 - m) x  (``known_region_coefficients``),
+        so where the mask is 1 the final sample is ``known`` and the rest is generated around it.  Needs no retraining.
+
+        ``known``: ``shape``; ``known_mask``: (B, T, H, W) or anything that broadcasts to it, values in [0, 1] (soft edges
+        are allowed); the mask in effect is ``known_mask * latent_mask[b, t]``: observed and absent frames are never touched.
+        ``sampler``: "ancestral" (fresh eps at every step), "ddim" with ``eta`` (eta = 0: ONE eps per chain, so the known
+        part follows the same ODE noise at every level) or "dpm_solver" (one eps per chain).  ``resample_steps`` = r > 1
+        (ancestral only): at every timestep above 0 the step is taken r times, the state re-noised by one forward step in
+        between (RePaint's resampling with jump length 1), r U-Net forwards per timestep.  Everything else as in
+        ``p_sample_loop`` / ``ddim_sample_loop`` / ``dpm_solver_sample_loop``; returns the final sample alone."""
+        if return_decoded and not self.can_decode():
+            raise NotImplementedError("known_region_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); "
+                                      "pass return_decoded=False for latents - refused BEFORE the chain runs")
+        final = None
+        for sample in self._known_region_chain(model, shape, known, known_mask, sampler, eta, resample_steps, noise,
+                                               clip_denoised, denoised_fn, model_kwargs, latent_mask, device, progress,
+                                               _reuse_buffers=True, _final_only=True):
+            final = sample
+        out = final["sample"].clone()
+        return self.decode(out) if return_decoded else out
+
+    def known_region_sample_loop_progressive(self, model, shape, known, known_mask, *, sampler="ancestral", eta=0.0,
+                                             resample_steps=1, noise=None, clip_denoised=True, denoised_fn=None,
+                                             model_kwargs=None, latent_mask=None, device=None, progress=False):
+        """Generator over {"sample", "pred_xstart"} for t = T-1 .. 0 of ``known_region_sample_loop``'s chain (one dict per
+        timestep, behind its last repeat); arguments are checked when it is called, not at the first ``next``."""
+        return self._known_region_chain(model, shape, known, known_mask, sampler, eta, resample_steps, noise, clip_denoised,
+                                        denoised_fn, model_kwargs, latent_mask, device, progress)
+
+    def _known_region_chain(self, model, shape, known, known_mask, sampler, eta, resample_steps, noise, clip_denoised,
+                            denoised_fn, model_kwargs, latent_mask, device, progress, _reuse_buffers=False, _final_only=False):
+        rule, fixed, repeats = self._known_region_check(shape, known, known_mask, sampler, eta, resample_steps, noise, latent_mask)
+        if device is None:
+            device = next(model.parameters()).device
+        B, T, _, H, W = shape
+        known = known.to(device=device, dtype=th.float32).contiguous()
+        mask = known_mask.to(device=device, dtype=th.float32).broadcast_to(B, T, H, W)
+        if latent_mask is not None:      # once, on the host side of the chain: frames that are not latent are never blended
+            mask = mask * latent_mask.to(device=device, dtype=th.float32).reshape(B, T, 1, 1)
+        return self._known_region_steps(rule, fixed, repeats, model, tuple(shape), known, mask.contiguous(), noise, clip_denoised,
+                                        denoised_fn, model_kwargs, device, progress, _reuse_buffers, _final_only)
+
+    def _known_region_steps(self, rule, fixed, repeats, model, shape, known, mask, noise, clip_denoised, denoised_fn,
+                            model_kwargs, device, progress, _reuse_buffers, _final_only):
+        from .unet import UNetVideoModel
+        n = self.num_timesteps
+        img = noise if noise is not None else th.randn(*shape, device=device)      # torch's generator: as the plain loops
+        gen = self._fork_generator(img.device)
+        eps = th.randn(*shape, device=img.device, generator=gen) if fixed else None
+        indices = list(range(n))[::-1]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        inner = getattr(model, "model", model)
+        inner = getattr(inner, "module", inner)
+        if isinstance(inner, UNetVideoModel) and img.is_cuda and denoised_fn is None and model_kwargs is not None:
+            s = self._known_region_sampler(inner, shape, clip_denoised, rule, fixed)
+            s.begin(img, model_kwargs, known=known, known_mask=mask, known_eps=eps)
+            if repeats == 1 and _final_only and not progress:
+                out = s.run(n - 1, n)
+                if s.chain_timed_out():      # the plain loops' protocol (_sample_loop)
+                    s.fall_back()
+                    s.begin(img, model_kwargs, known=known, known_mask=mask, known_eps=eps)
+                    out = s.run(n - 1, n)
+                yield {k: out[k] for k in ("sample", "pred_xstart")}
+                return
+            seed0 = s.seed.clone() if repeats > 1 else None
+            for m, i in enumerate(indices):
+                # host-driven resampling over the single-step graph: step (clock reset by step itself), re-noise, again
+                reps = repeats if i > 0 else 1
+                for k in range(reps):
+                    if seed0 is not None:
+                        th.add(seed0, self._repeat_seed_offset(k), out=s.seed)
+                    out = s.step(i)
+                    if k < reps - 1:
+                        s.renoise()
+                if (m & 63) == 63 or i == 0:
+                    if s.chain_timed_out():
+                        s.fall_back()
+                        raise RuntimeError("a persistent level chain timed out during this sampling chain (lfvdm_level_chain): "
+                                           "the states yielded since the last check are not valid; the plan now runs one "
+                                           "launch per stage - run the chain again")
+                yield {k: (out[k] if _reuse_buffers else out[k].clone()) for k in ("sample", "pred_xstart")}
+            return
+        # the slow path: the per-step methods, then the same blend (the kernel on the GPU, plain torch on the CPU)
+        tb = self.known_region_tables(img.device)
+        seed0 = th.empty(1, dtype=th.int64, device=img.device).random_(generator=gen) if img.is_cuda else None
+        m5 = mask.unsqueeze(2)
+        prev = None
+        for i in indices:
+            t = th.full((shape[0],), i, device=img.device, dtype=th.long)
+            reps = repeats if i > 0 else 1
+            for k in range(reps):
+                with th.no_grad():
+                    if rule[0] == "ancestral":
+                        out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                            model_kwargs=model_kwargs)
+                    elif rule[0] == "dpmpp2m":
+                        out = self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                     model_kwargs=model_kwargs, prev_pred_xstart=prev)
+                        prev = out["pred_xstart"]
+                    else:
+                        out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                               model_kwargs=model_kwargs, eta=rule[1])
+                    img = out["sample"].clone(memory_format=th.contiguous_format)
+                    if img.is_cuda:
+                        seed = seed0 + self._repeat_seed_offset(k)
+                        nat.known_blend(img, known, mask, t, tb["a"], tb["s"], eps=eps, seed=None if fixed else seed)
+                        if k < reps - 1:
+                            nat.renoise(img, t, tb["sqrt_1mbeta"], tb["sqrt_beta"], seed)
+                    else:
+                        z = eps if fixed else th.randn(*shape, generator=gen)
+                        v = _bshape(tb["a"][t], 5) * known + _bshape(tb["s"][t], 5) * z
+                        img = th.where(m5 == 0, img, th.where(m5 == 1, v, m5 * v + (1 - m5) * img))
+                        if k < reps - 1:
+                            img = _bshape(tb["sqrt_1mbeta"][t], 5) * img + _bshape(tb["sqrt_beta"][t], 5) * th.randn(*shape, generator=gen)
+            yield {"sample": img, "pred_xstart": out["pred_xstart"]}
+
     def model_timestep_table(self, device):
         """Per-step model timestep (float) — identity/rescale here, remap in SpacedDiffusion."""
         ts = np.arange(self.num_timesteps, dtype=np.float64)
@@ -1143,8 +1355,42 @@ class GraphSampler(ReplayedStep):
         if self.plan.time_steps and self.plan.time_ring:
             self.K = min(self.K, self.plan.time_ring // 2)     # a graph launch must not walk more than half the R ring
         self.graph_k = None
+        # known-region sampling (``enable_known_region``): static buffers the captured step's last launch reads
+        self.known = self.known_mask = self.known_eps = self.known_noise = self.known_tb = None
+
+    def enable_known_region(self, fixed_noise, record_noise=False):
+        """Make this a known-region sampler, before its first chain: the captured step then ENDS with the blend launch
+        (lfvdm_known_blend) over the static buffers ``known`` (the state's shape), ``known_mask`` (B, T, H, W) and - with
+        ``fixed_noise``, the deterministic rules - ``known_eps``; ``begin`` refills them, so every chain replays the same
+        graphs.  Without ``fixed_noise`` the blend draws fresh noise under the chain's ``seed`` (its own Philox stream);
+        ``record_noise`` keeps what it drew in ``known_noise`` (tests)."""
+        if self.graph is not None or self.graph_k is not None:
+            raise RuntimeError("enable_known_region comes before the sampler's first chain: its graphs are captured already")
+        B, T, _, H, W = self.shape
+        dev = self.plan.dev
+        self.known_tb = self.diffusion.known_region_tables(dev)
+        self.known = th.zeros(self.shape, device=dev)
+        self.known_mask = th.zeros(B, T, H, W, device=dev)
+        self.known_eps = th.zeros(self.shape, device=dev) if fixed_noise else None
+        self.known_noise = th.zeros(self.shape, device=dev) if record_noise and not fixed_noise else None
 
     def _step_body(self):
+        """The denoising step; a known-region sampler then puts the known part back at the level the step arrived at
+        (``t_buf`` still holds the timestep the step consumed)."""
+        self._denoise_body()
+        if self.known is not None:
+            nat.known_blend(self.plan.x_in, self.known, self.known_mask, self.t_buf, self.known_tb["a"], self.known_tb["s"],
+                            eps=self.known_eps, seed=self.seed, noise_out=self.known_noise)
+            self.extra_launches += 1
+
+    def renoise(self):
+        """Resampling: the state one forward step back up, to the level of the timestep the last step consumed (the clock
+        still holds it), with fresh noise under the chain's seed (lfvdm_renoise: a Philox stream of its own).  One eager
+        launch between replays; the next ``step`` of the same timestep puts the clock back."""
+        tb = self.diffusion.known_region_tables(self.plan.dev)
+        nat.renoise(self.plan.x_in, self.t_buf, tb["sqrt_1mbeta"], tb["sqrt_beta"], self.seed)
+
+    def _denoise_body(self):
         """The clock and the forward, then at most one update launch, chosen by where the noise comes from."""
         import os
         pl = self.plan
@@ -1183,11 +1429,19 @@ class GraphSampler(ReplayedStep):
         nat.update_x0(pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, self.clip, pl.x_in,
                       self.pred)
 
-    def begin(self, img, model_kwargs):
+    def begin(self, img, model_kwargs, known=None, known_mask=None, known_eps=None):
         # callers that drive step() / run() themselves: checked once per chain, here - unless whoever ran the previous
         # chain has looked already (p_sample_loop does, behind run(): one host synchronisation per chain, not two)
         if self._abort_unchecked and self.chain_timed_out():
             self.fall_back()
+        if (self.known is None) != (known is None) or (self.known_eps is None) != (known_eps is None):
+            raise ValueError("known / known_mask (and known_eps under a fixed-noise rule) go to a sampler made with "
+                             "enable_known_region, and to no other")
+        if known is not None:      # this chain's known region -> the static buffers (no draw from torch's generator)
+            self.known.copy_(known)
+            self.known_mask.copy_(known_mask)
+            if known_eps is not None:
+                self.known_eps.copy_(known_eps)
         self._begin_chain(img, model_kwargs)
         self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
         if self.multistep:

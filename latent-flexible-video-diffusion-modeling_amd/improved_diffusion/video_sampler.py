@@ -33,7 +33,7 @@ def window_inputs(samples, obs_frame_indices, latent_frame_indices, device=None)
 
 
 @th.no_grad()
-def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=True):
+def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=True, known_video=None, known_mask=None):
     """batch: (B, T, C, H, W); the first ``args.n_obs`` frames are observed, the rest are generated.
 
     args needs: n_obs, max_frames, max_latent_frames, sampling_scheme, clip_denoised, device and optionally
@@ -41,7 +41,19 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     chain; in the reference ``--use_ddim`` only renames the results folder, here it selects the sampler), use_dpm_solver
     (DPM-Solver++(2M) instead; together with use_ddim: ValueError).  Returns ``(samples, indices_used)``
     with ``samples`` on batch's device and ``indices_used`` the list of (obs, latent) index lists per window.
+
+    ``known_video`` (B, T, C, H, W) with ``known_mask`` (B, T, H, W), both or neither (not in the reference): the part of
+    the video's generated frames that is known - inpainting, outpainting.  Each window gathers its frames of the two and
+    runs ``known_region_sample_loop`` under the sampler the flags above select; where the mask is 1 the sampled frames
+    equal ``known_video``.
     """
+    if (known_video is None) != (known_mask is None):
+        raise ValueError("known_video and known_mask come together")
+    if known_video is not None:
+        if tuple(known_video.shape) != tuple(batch.shape):
+            raise ValueError(f"known_video has the shape of batch {tuple(batch.shape)}, got {tuple(known_video.shape)}")
+        if tuple(known_mask.shape) != (batch.shape[0], batch.shape[1], *batch.shape[3:]):
+            raise ValueError(f"known_mask is (B, T, H, W) of batch, got {tuple(known_mask.shape)}")
     B, T = batch.shape[:2]
     use_dpm_solver = bool(getattr(args, "use_dpm_solver", False))
     if use_dpm_solver and getattr(args, "use_ddim", False):
@@ -57,6 +69,8 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     batch_dev = batch.to(device) if just_get_indices else None
     decoded = getattr(diffusion, "diffusion_space", None) in (None, "pixel")
     rows = th.arange(B, device=device)[:, None]
+    if known_video is not None:
+        known_video, known_mask = known_video.to(device), known_mask.to(device=device, dtype=th.float32)
     indices_used = []
     while True:
         scheme.set_videos(samples)         # only the adaptive schemes look at the frames
@@ -70,6 +84,13 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
         n_lat = len(lat_idx[0])
         if just_get_indices:
             local = batch_dev[rows, frame_indices]
+        elif known_video is not None:
+            sampler = "dpm_solver" if use_dpm_solver else "ddim" if getattr(args, "use_ddim", False) else "ancestral"
+            local = diffusion.known_region_sample_loop(
+                model, tuple(x0.shape), known_video[rows, frame_indices], known_mask[rows, frame_indices], sampler=sampler,
+                eta=getattr(args, "ddim_eta", 0.0), clip_denoised=args.clip_denoised,
+                model_kwargs=dict(frame_indices=frame_indices, x0=x0, obs_mask=obs_mask, latent_mask=latent_mask),
+                latent_mask=latent_mask, return_decoded=decoded)
         elif use_dpm_solver:
             local = diffusion.dpm_solver_sample_loop(
                 model, tuple(x0.shape), clip_denoised=args.clip_denoised,
