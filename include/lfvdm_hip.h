@@ -70,7 +70,12 @@ typedef struct lfvdm_conv_args {
     int32_t N;        /* samples (B*T) */
     int32_t Hs, Ws;   /* spatial size of the stored source */
     int32_t up;       /* 1: source is nearest-upsampled x2 on the fly; 2: zero-insertion x2 (the data
-                       * gradient of a stride-2 conv is this conv on the transposed-flipped weights) */
+                       * gradient of a stride-2 conv is this conv on the transposed-flipped weights);
+                       * 3: nearest x2 by output parity class - four 2x2 convolutions over the source grid, W packed
+                       * by lfvdm_pack_conv_weight_up2x (K = 4*C0 instead of 9*C0; same result as up = 1 up to the
+                       * fp32 rounding of the summed weights).  Legal for ksize 3, stride 1, one source, no 1x1 skip
+                       * segment, no gn_out, no resA, LFVDM_OUT_ROWS (bias and res allowed); LFVDM_E_UNSUPPORTED
+                       * otherwise or with LFVDM_CONV_NO_UP_PARITY set: fall back to up = 1 on the ordinary pack */
     int32_t stride;   /* 1 or 2 */
     int32_t ksize;    /* 3 (pad 1) or 1 (pad 0) */
     int32_t Ho, Wo;   /* output spatial size */
@@ -154,6 +159,11 @@ int lfvdm_conv_wgrad_grouped(const lfvdm_wgrad_job* jobs_dev, int njobs, int tot
 
 /* OIHW [Cout][Cin][k][k] -> [Cout][k*k][Cin] (k in {1,3}); state-dict layout stays OIHW. */
 int lfvdm_pack_conv_weight(const float* w_oihw, float* w_packed, int Cout, int Cin, int ksize, void* stream);
+/* OIHW [Cout][Cin][3][3] -> [4][Cout][4][Cin] for lfvdm_conv_args::up = 3: class = 2*py + px (parity of the output pixel),
+ * tap = 2*a + b over the two source rows / columns under it, ascending.  Source row a collects filter rows {0} | {1,2}
+ * (py = 0) or {0,1} | {2} (py = 1), columns likewise with px.  The sums are fp32 in a fixed order - rows first (per
+ * filter column, ascending row), then columns (ascending) - so the pack is reproducible bit for bit. */
+int lfvdm_pack_conv_weight_up2x(const float* w_oihw, float* w_packed, int Cout, int Cin, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Backward of the convolution / linear (autograd of nn.Conv2d / nn.Linear in the reference,

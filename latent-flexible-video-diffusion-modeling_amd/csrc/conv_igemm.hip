@@ -47,6 +47,13 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_kernel(const lfv
     conv_igemm_body<WM, WN, WK, NT, KCH, SIMPLE, GL, false>(p, hyb_nfull, hyb_kz, par_mt, ChainCtx{});
 }
 
+// the nearest-2x parity-class form (up == 3): the general body with the class arithmetic compiled in (see the body)
+template <int WM, int WN, int WK, int NT, int KCH, int GL>
+__global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_up2x_kernel(const lfvdm_conv_args p_in, int par_mt) {
+    const lfvdm_conv_args p = p_in;
+    conv_igemm_body<WM, WN, WK, NT, KCH, false, GL, false, true>(p, 0, 0, par_mt, ChainCtx{});
+}
+
 __global__ void pack_conv_weight_kernel(const float* __restrict__ w, float* __restrict__ o, int Cout, int Cin, int taps) {
     // o[co][tap][ci] = w[co][ci][tap]
     const size_t total = (size_t)Cout * Cin * taps;
@@ -59,6 +66,33 @@ __global__ void pack_conv_weight_kernel(const float* __restrict__ w, float* __re
     }
 }
 
+__global__ void pack_conv_weight_up2x_kernel(const float* __restrict__ w, float* __restrict__ o, int Cout, int Cin) {
+    // o[2*py + px][co][2*a + b][ci]: the 3x3 filter of a nearest-2x upsampled source folded onto the 2x2 source pixels under
+    // an output pixel of parity (py, px).  Source row a of class py collects filter rows {0}, {1, 2} (py = 0) or {0, 1}, {2}
+    // (py = 1); columns likewise with px.  Fixed fp32 order, rows first, then columns: for each collected filter column the
+    // filter rows are added (ascending row), then the column sums are added (ascending column) - single rounded adds, so
+    // the pack is reproducible bit for bit
+    const size_t total = (size_t)16 * Cout * Cin;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int ci = (int)(i % Cin);
+        size_t t2 = i / Cin;
+        const int tap = (int)(t2 & 3);
+        t2 >>= 2;
+        const int co = (int)(t2 % Cout), cls = (int)(t2 / Cout);
+        const int py = cls >> 1, px = cls & 1, a = tap >> 1, b = tap & 1;
+        const int r0 = a == 0 ? 0 : 1 + py, r1 = a == 0 ? py : 2;        // filter rows r0..r1 land on source row a
+        const int c0 = b == 0 ? 0 : 1 + px, c1 = b == 0 ? px : 2;
+        const float* f = w + ((size_t)co * Cin + ci) * 9;
+        float acc = 0.f;
+        for (int c = c0; c <= c1; ++c) {
+            float colsum = f[3 * r0 + c];
+            if (r1 > r0) colsum = __fadd_rn(colsum, f[3 * r1 + c]);
+            acc = c == c0 ? colsum : __fadd_rn(acc, colsum);
+        }
+        o[i] = acc;
+    }
+}
+
 template <int WM, int WN, int WK, int NT, int KCH, bool SIMPLE, int GL>
 int launch_pro(const lfvdm_conv_args* a, hipStream_t s, long M, int kz) {
     using CF = Cfg<WM, WN, WK, NT, KCH, GL>;
@@ -68,6 +102,7 @@ int launch_pro(const lfvdm_conv_args* a, hipStream_t s, long M, int kz) {
         return rc;
     const long MT = (M + CF::BM - 1) / CF::BM, NT2 = (a->Cout + CF::BN - 1) / CF::BN;
     if constexpr (!SIMPLE) {
+        if (a->up == 3) return LFVDM_E_UNSUPPORTED;       // (launch_up2x)
         if (parity_classes(a)) {
             const long MTc = (M / 4 + CF::BM - 1) / CF::BM;
             if (kz == kHybridKz || 4 * MTc >= (1L << 20)) return LFVDM_E_UNSUPPORTED;
@@ -100,15 +135,33 @@ int launch_pro(const lfvdm_conv_args* a, hipStream_t s, long M, int kz) {
     return LFVDM_OK;
 }
 
+// the nearest-2x parity-class form: grid (4 classes x row tiles of the source grid, filter tiles, K slices)
+template <int WM, int WN, int WK, int NT, int KCH, int GL>
+int launch_up2x(const lfvdm_conv_args* a, hipStream_t s, long M, int kz) {
+    using CF = Cfg<WM, WN, WK, NT, KCH, GL>;
+    if (CF::LDS_BYTES > 160 * 1024 || !up_parity(a)) return LFVDM_E_UNSUPPORTED;
+    static DynLdsLimit limit;
+    if (int rc = limit.ensure(reinterpret_cast<const void*>(&conv_igemm_up2x_kernel<WM, WN, WK, NT, KCH, GL>), CF::LDS_BYTES)) return rc;
+    const long MTc = (M / 4 + CF::BM - 1) / CF::BM, NT2 = (a->Cout + CF::BN - 1) / CF::BN;
+    if (kz == kHybridKz || 4 * MTc >= (1L << 20)) return LFVDM_E_UNSUPPORTED;
+    hipLaunchKernelGGL((conv_igemm_up2x_kernel<WM, WN, WK, NT, KCH, GL>), dim3((unsigned)(4 * MTc), (unsigned)NT2, (unsigned)kz),
+                       dim3(CF::NTHREADS), CF::LDS_BYTES, s, *a, (int)MTc);
+    LFVDM_CHECK_LAUNCH();
+    return LFVDM_OK;
+}
+
 template <int WM, int WN, int WK, int NT, int KCH>
 int launch_kc(const lfvdm_conv_args* a, hipStream_t s, long M, int kz, int gl) {
     const bool simple = a->C1 == 0 && a->s2C0 + a->s2C1 == 0 && a->up == 0;
+    const bool up3 = a->up == 3;
     if constexpr (glds_lds_bytes(WM, WN, WK, NT, KCH, 3) <= 160 * 1024) {
         if (gl == 3) return simple ? launch_pro<WM, WN, WK, NT, KCH, true, 3>(a, s, M, kz)
+                            : up3  ? launch_up2x<WM, WN, WK, NT, KCH, 3>(a, s, M, kz)
                                    : launch_pro<WM, WN, WK, NT, KCH, false, 3>(a, s, M, kz);
     }
     if constexpr (glds_lds_bytes(WM, WN, WK, NT, KCH, 2) <= 160 * 1024) {
         return simple ? launch_pro<WM, WN, WK, NT, KCH, true, 2>(a, s, M, kz)
+               : up3  ? launch_up2x<WM, WN, WK, NT, KCH, 2>(a, s, M, kz)
                       : launch_pro<WM, WN, WK, NT, KCH, false, 2>(a, s, M, kz);
     }
     return LFVDM_E_UNSUPPORTED;
@@ -148,19 +201,20 @@ double model_cycles(const TileCfg& c, int Cout, long M, int NK, int kch, int kz)
 
 Pick pick_cfg(const lfvdm_conv_args* a, long M) {
     const int Cin = a->C0 + a->C1, C2 = a->s2C0 + a->s2C1;
+    const int ktaps = a->up == 3 ? 4 : a->ksize * a->ksize;     // nearest-2x by parity class: four pre-summed taps per class
     if (a->tune > 0) {   // explicit choice (autotuner); fall through to the model if it is not legal here
         const int t = a->tune - 1;
         const int id = t & 15, kch = (t & 16) ? 64 : 32, kz = kKzTable[(t >> 5) & 7], gl = ((t >> 8) & 3) + 1;
-        if (cfg_valid(a, id, kch, kz, gl)) return {id, kch, a->ksize * a->ksize * (Cin / kch) + C2 / kch, kz, gl};
+        if (cfg_valid(a, id, kch, kz, gl)) return {id, kch, ktaps * (Cin / kch) + C2 / kch, kz, gl};
     }
     static const int forced = getenv("LFVDM_CONV_CFG") ? atoi(getenv("LFVDM_CONV_CFG")) : -1;  // tuning aid
-    Pick best = {-1, 32, a->ksize * a->ksize * (Cin / 32) + C2 / 32, 1, 2};
+    Pick best = {-1, 32, ktaps * (Cin / 32) + C2 / 32, 1, 2};
     double best_t = 1e30;
     for (int i = 0; i < kNumCfgs; ++i) {
         if (forced >= 0 && i != forced) continue;
         for (int kch = 32; kch <= 64; kch += 32) {
             if (!cfg_valid(a, i, kch, 1, 2)) continue;          // the built-in model never splits K over workgroups
-            const int NK = a->ksize * a->ksize * (Cin / kch) + C2 / kch;
+            const int NK = ktaps * (Cin / kch) + C2 / kch;
             const double est = model_cycles(kCfgs[i], a->Cout, M, NK, kch, 1);
             if (est < best_t) { best_t = est; best = {i, kch, NK, 1, 2}; }
         }
@@ -196,6 +250,9 @@ extern "C" int lfvdm_conv_igemm(const lfvdm_conv_args* a, void* stream) {
     if (Cin % 32 || a->C0 % 32 || C2 % 32 || a->s2C0 % 32) return LFVDM_E_SHAPE;
     if (a->ksize != 1 && a->ksize != 3) return LFVDM_E_SHAPE;
     if (a->stride != 1 && a->stride != 2) return LFVDM_E_SHAPE;
+    if (a->up < 0 || a->up > 3) return LFVDM_E_SHAPE;
+    // nearest-2x by parity class runs on its own weight pack and in the class form only: anything else is refused
+    if (a->up == 3 && !up_parity(a)) return LFVDM_E_UNSUPPORTED;
     if (a->C1 > 0 && !a->src1) return LFVDM_E_SHAPE;
     if (C2 > 0 && (!a->W2 || !a->s2src0 || (a->s2C1 > 0 && !a->s2src1))) return LFVDM_E_SHAPE;
     // the operand prologue (GroupNorm coefficients applied while staging) is gone: normalise with lfvdm_gn_apply or a
@@ -251,6 +308,15 @@ extern "C" int lfvdm_pack_conv_weight(const float* w, float* o, int Cout, int Ci
     const size_t total = (size_t)Cout * Cin * ksize * ksize;
     const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
     hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, o, Cout, Cin, ksize * ksize);
+    LFVDM_CHECK_LAUNCH();
+    return LFVDM_OK;
+}
+
+extern "C" int lfvdm_pack_conv_weight_up2x(const float* w, float* o, int Cout, int Cin, void* stream) {
+    if (Cout <= 0 || Cin <= 0) return LFVDM_E_SHAPE;
+    const size_t total = (size_t)16 * Cout * Cin;
+    const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
+    hipLaunchKernelGGL(pack_conv_weight_up2x_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, o, Cout, Cin);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }

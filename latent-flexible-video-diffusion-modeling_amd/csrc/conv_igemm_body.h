@@ -122,7 +122,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t whole_rsrc(const float* base) 
 
 // CHAIN = false: the body of conv_igemm_kernel (one workgroup = blockIdx).  CHAIN = true: one work item of a chain stage;
 // -> false if the chain was aborted while this item waited (the caller leaves the kernel).
-template <int WM, int WN, int WK, int NT, int KCH, bool SIMPLE, int GL, bool CHAIN>
+// UP3 = true: the nearest-2x parity-class form (up == 3), an instance of its own - as run-time selects in the general
+// instance its handful of scalar instructions per chunk cost the concat / skip-segment launches 1.5-3.4 us each (measured).
+template <int WM, int WN, int WK, int NT, int KCH, bool SIMPLE, int GL, bool CHAIN, bool UP3 = false>
 __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hyb_nfull, int hyb_kz, int par_mt, const ChainCtx& cx) {
     using CF = Cfg<WM, WN, WK, NT, KCH, GL>;
     static_assert(GL == 2 || GL == 3, "two or three LDS-DMA stages");
@@ -146,7 +148,13 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
     // 2 or 4 of the 9 depending on (oy & 1, ox & 1).  A workgroup takes rows of ONE parity class - enumerated on the
     // source grid, M = N * Hs * Ws per class - and loops over that class's taps only: 9/4 taps per output pixel on
     // average instead of 9 with three quarters of the staged pieces zero.  Heavy classes (4 taps) get the low block ids.
-    const bool par = !SIMPLE && !CHAIN && par_mt > 0;
+    // Nearest-2x source by parity class (up == 3, the same grid): the two source rows under output row 2i + py are i - 1 + py
+    // and i + py, each read by one or two of the three filter rows, and the columns likewise - every class is a 2x2
+    // convolution over the SOURCE grid on pre-summed weights (lfvdm_pack_conv_weight_up2x: [class][Cout][4 taps][Cin]), K =
+    // 4 * Cin instead of 9 * Cin.  A source row -1 / Hs is the padded row of the upsampled image: it zero-fills.
+    static_assert(!UP3 || (!SIMPLE && !CHAIN), "the nearest-2x class form is a general, per-launch instance");
+    constexpr bool nn2 = UP3;                                    // (the launcher passes par_mt > 0)
+    const bool par = UP3 || (!SIMPLE && !CHAIN && par_mt > 0);
     int pcls = 0;
     if (par) pcls = 3 - div_small((int)blockIdx.x, par_mt);      // (never in a chain)
     const int ppy = pcls >> 1, ppx = pcls & 1;
@@ -196,7 +204,7 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
     const int n0 = by * BN;
     const int Cin = p.C0 + p.C1;
     const int taps = p.ksize * p.ksize;
-    const int ltaps = par ? (1 + ppy) * (1 + ppx) : taps;      // taps the K loop walks (parity classes: the live ones)
+    const int ltaps = nn2 ? 4 : par ? (1 + ppy) * (1 + ppx) : taps;      // taps the K loop walks (parity classes: the live ones)
     const int NK1 = ltaps * (int)((unsigned)Cin / (unsigned)KC);
     const int NK = NK1 + (int)((unsigned)(p.s2C0 + p.s2C1) / (unsigned)KC);
 
@@ -371,7 +379,8 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
     // SIMPLE: one raw source.  Otherwise also the virtual concat (src0 | src1) and the fused 1x1 skip segment
     // (s2src0 | s2src1 at output resolution, weights W2); the buffer descriptor of a chunk is built from scalar
     // selects of base pointer and size (holding six descriptors at once spills SGPRs to scratch).
-    const int wld = taps * Cin, w2ld = p.s2C0 + p.s2C1;
+    const int wld = (nn2 ? 4 : taps) * Cin, w2ld = p.s2C0 + p.s2C1;
+    const float* Wmain = nn2 ? p.W + (size_t)pcls * p.Cout * wld : p.W;      // nearest-2x classes: the class's own weight block
     const unsigned pixA = (unsigned)p.N * p.Hs * p.Ws * 4u;
     auto desc = [](const float* base, unsigned bytes) {
         return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
@@ -407,8 +416,9 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
                 aoff1[j] = (unsigned)ri[j].pix * p.C1 * 4u + q16;
                 soff0[j] = (unsigned)ri[j].m * p.s2C0 * 4u + q16;
                 soff1[j] = (unsigned)ri[j].m * p.s2C1 * 4u + q16;
-                upy[j] = ri[j].oy * p.stride;
-                upx[j] = ri[j].ox * p.stride;
+                // (nearest-2x classes: source row / column of tap (0, 0), -1 at the top / left border)
+                upy[j] = nn2 ? (ri[j].oy >> 1) + ppy - 1 : ri[j].oy * p.stride;
+                upx[j] = nn2 ? (ri[j].ox >> 1) + ppx - 1 : ri[j].ox * p.stride;
                 upb[j] = (unsigned)ri[j].n * p.Hs * p.Ws;
                 upq[j] = q16;
             }
@@ -427,7 +437,7 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
         }
     }
     const int k3 = p.ksize == 3 ? 1 : 0;
-    const int pC0 = p.C0, pC1 = p.C1, pS0 = p.s2C0, pS1 = p.s2C1, pWs = p.Ws;   // by-value copies for the selects below
+    const int pC0 = p.C0, pC1 = p.C1, pS0 = p.s2C0, pS1 = p.s2C1, pWs = p.Ws, pHs = p.Hs;   // by-value copies for the selects below
     // (channel chunk, tap) of the next chunk: the chunks of a k-group are issued in order, so the pair is carried as
     // scalar state and advanced after every issue - one division per kernel instead of one per chunk.  Chunks past the
     // group's slice (kc_raw >= kend: padding iterations of a group that owns fewer chunks) pass out-of-range offsets
@@ -438,7 +448,7 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
         const bool main_seg = SIMPLE ? true : kc_raw < NK1;
         const int ci = main_seg ? nx_ci : kc_raw - NK1, cc = ci * KC;
         int tap = main_seg ? nx_tap : 0;
-        if (par) {      // l-th live tap of the class: dy = 0 (even rows) or -1, +1 (odd rows), the same for dx
+        if (par && !nn2) {      // l-th live tap of the class: dy = 0 (even rows) or -1, +1 (odd rows), the same for dx
             const int ty = ppx ? (tap >> 1) : tap, tx = ppx ? (tap & 1) : 0;
             tap = 3 * (ppy ? 2 * ty : 1) + (ppx ? 2 * tx : 1);
         }
@@ -449,13 +459,14 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
         const int cl = second ? cc - c0 : cc;
         const int Csrc = sel(main_seg, sel(second, pC1, pC0), sel(second, pS1, pS0));
         const int t3 = tap / 3, km = main_seg ? k3 : 0;                // branch-free: no tap offset for 1x1 / skip chunks
-        const int dy = (t3 - 1) * km, dx = (tap - t3 * 3 - 1) * km;
+        // (nearest-2x classes: tap = 2 * a + b, offsets (a, b) from the source pixel of tap (0, 0))
+        const int dy = nn2 ? tap >> 1 : (t3 - 1) * km, dx = nn2 ? tap & 1 : (tap - t3 * 3 - 1) * km;
         const int ashift = ((dy * pWs + dx) * Csrc + cl) * 4;          // bytes, may be negative
-        const int upm = SIMPLE ? 0 : sel(main_seg, p.up, 0);            // 0 none, 1 nearest x2, 2 zero insertion (wave-uniform)
+        const int upm = SIMPLE ? 0 : sel(main_seg, p.up, 0);   // 0 none, 1 nearest x2, 2 zero insertion, 3 nearest x2 by class (wave-uniform)
         const unsigned wshift = live ? (unsigned)(main_seg ? tap * Cin + cc : cc) * 4u : kOOB;
-        const unsigned tapbit = live ? (main_seg ? (1u << tap) : 0x80000000u) : 0u;
+        const unsigned tapbit = live ? (main_seg && !nn2 ? (1u << tap) : 0x80000000u) : 0u;    // (nearest-2x classes: range-checked below)
         const float* abase = SIMPLE ? p.src0 : sel(main_seg, sel(second, p.src1, p.src0), sel(second, p.s2src1, p.s2src0));
-        const float* bbase = SIMPLE ? p.W : sel(main_seg, p.W, p.W2);
+        const float* bbase = SIMPLE ? p.W : sel(main_seg, Wmain, p.W2);
         const __amdgpu_buffer_rsrc_t rsA = desc(abase, sel(main_seg, pixA, (unsigned)M * 4u) * (unsigned)Csrc);
         const __amdgpu_buffer_rsrc_t rsB = desc(bbase, (unsigned)p.Cout * (unsigned)sel(main_seg, wld, w2ld) * 4u);
         float* As = gbase + stage * CF::STAGE + wmn * 256;             // this wave's first piece
@@ -470,7 +481,12 @@ __device__ __forceinline__ bool conv_igemm_body(const lfvdm_conv_args& p, int hy
             }
             unsigned off = (amsk[j] & tapbit) ? base + (unsigned)ashift : kOOB;
             if constexpr (!SIMPLE) {
-                if (upm) {                  // scalar branch
+                if constexpr (UP3) {        // (iy, ix) is a SOURCE pixel; outside the map = the padded border of the upsampled image
+                    const int iy = upy[j] + dy, ix = upx[j] + dx;
+                    const bool ok = (amsk[j] & tapbit) && (unsigned)iy < (unsigned)pHs && (unsigned)ix < (unsigned)pWs;
+                    const unsigned px = upb[j] + (unsigned)(iy * pWs + ix);
+                    off = ok ? px * (unsigned)Csrc * 4u + (unsigned)cl * 4u + upq[j] : kOOB;
+                } else if (upm) {           // scalar branch
                     const int iy = upy[j] + dy, ix = upx[j] + dx;       // inside the upsampled image iff the tap bit is set
                     const bool ok = (amsk[j] & tapbit) && (upm == 1 || ((iy | ix) & 1) == 0);
                     const unsigned px = upb[j] + (unsigned)((iy >> 1) * pWs + (ix >> 1));
@@ -952,10 +968,19 @@ inline HybridPlan hybrid_plan(long tiles) {
 }
 
 // zero-inserted source handled by output parity classes (see the kernel): the data gradient of a stride-2 convolution
+inline bool parity_form_ok(const lfvdm_conv_args* a) {
+    return a->ksize == 3 && a->stride == 1 && a->C1 == 0 && a->s2C0 + a->s2C1 == 0 && !a->gn_out && !a->resA &&
+           a->out_mode == LFVDM_OUT_ROWS;
+}
+// nearest-2x source as four 2x2 convolutions on pre-summed weights (up == 3, see the kernel): legal exactly where the
+// zero-insertion classes are; there is no other way to run up == 3 (the launch is refused, callers fall back to up = 1).
+// LFVDM_CONV_NO_UP_PARITY (A/B aid) refuses the form; it is read per call, so a process can build plans both ways.
+inline bool up_parity(const lfvdm_conv_args* a) {
+    return a->up == 3 && parity_form_ok(a) && getenv("LFVDM_CONV_NO_UP_PARITY") == nullptr;
+}
 inline bool parity_classes(const lfvdm_conv_args* a) {
     static const bool off = getenv("LFVDM_CONV_NO_PARITY") != nullptr;        // A/B aid
-    return !off && a->up == 2 && a->ksize == 3 && a->stride == 1 && a->C1 == 0 && a->s2C0 + a->s2C1 == 0 && !a->gn_out &&
-           !a->resA && a->out_mode == LFVDM_OUT_ROWS;
+    return (!off && a->up == 2 && parity_form_ok(a)) || up_parity(a);
 }
 
 // LDS bytes of a configuration with `gl` stages
@@ -1018,9 +1043,10 @@ bool cfg_valid(const lfvdm_conv_args* a, int id, int kch, int kz, int gl) {
     if (a->gn_out && !gn_tile_ok(a, BM, BN)) return false;
     const bool can64 = Cin % 64 == 0 && a->C0 % 64 == 0 && C2 % 64 == 0 && a->s2C0 % 64 == 0;
     if (kch == 64 && (!can64 || c.NT > 1)) return false;
+    if (a->up == 3 && !up_parity(a)) return false;
     const bool pc = parity_classes(a);
-    // (parity classes: the lightest class walks ONE tap)
-    const int NK = pc ? Cin / kch : a->ksize * a->ksize * (Cin / kch) + C2 / kch;
+    // (zero-insertion classes: the lightest class walks ONE tap; nearest-2x classes: four taps each)
+    const int NK = a->up == 3 ? 4 * (Cin / kch) : pc ? Cin / kch : a->ksize * a->ksize * (Cin / kch) + C2 / kch;
     if (c.WK > NK) return false;
     if (pc && kz == kHybridKz) return false;
     if (glds_lds_bytes(c.WM, c.WN, c.WK, c.NT, kch, gl) > 160 * 1024) return false;

@@ -237,7 +237,7 @@ inline bool decode_chain_code(const lfvdm_conv_args* a, Pick2* pk) {
 bool conv_stage_ok(const lfvdm_conv_args* a, Pick2* pk) {
     if (!decode_chain_code(a, pk)) return false;
     if ((pk->id != 6 && pk->id != 2) || pk->kch != 32 || pk->kz < 1 || pk->kz > 8 || (pk->gl != 2 && pk->gl != 3)) return false;
-    if (a->out_mode != LFVDM_OUT_ROWS || a->coefA || a->coefB || a->resA || parity_classes(a) || a->up == 2) return false;
+    if (a->out_mode != LFVDM_OUT_ROWS || a->coefA || a->coefB || a->resA || parity_classes(a) || a->up >= 2) return false;
     const int Cin = a->C0 + a->C1, C2 = a->s2C0 + a->s2C1;
     if (a->N <= 0 || a->Cout <= 0 || Cin <= 0 || Cin % 32 || a->C0 % 32 || C2 % 32 || a->s2C0 % 32 || a->Cout % 4 || a->ldo % 4) return false;
     if (a->res && a->ldr % 4) return false;

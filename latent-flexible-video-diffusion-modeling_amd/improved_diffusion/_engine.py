@@ -186,6 +186,15 @@ class Plan:
         self.packs.append((weight, out) if (c0, c1) == (0, Cin) else (weight, out, c0, c1))
         return out
 
+    def packed_up2x(self, weight):
+        """Pre-summed [4 classes][Cout][4 taps][Cin] pack of a 3x3 weight for a nearest-2x conv run with up = 3
+        (lfvdm_pack_conv_weight_up2x); refreshed with the ordinary packs."""
+        Cout, Cin, k, _ = weight.shape
+        assert k == 3
+        out = self.buf(4, Cout, 4, Cin)
+        self.packs.append((weight, out, "up2x"))
+        return out
+
     def add(self, fn, *args):
         self.steps.append((fn, args))
 
@@ -701,8 +710,21 @@ class Plan:
         (x, Cc), = cur["parts"]
         Ho, Wo = (((H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1) if down else (2 * H, 2 * W))
         out = self.buf(N * Ho * Wo, Cc)
-        nact = self._final_conv(dict(src0=x, C0=Cc, N=N, Hs=H, Ws=W, up=0 if down else 1, stride=2 if down else 1, Ho=Ho, Wo=Wo,
-                                     W=self.packed(conv.weight), bias=conv.bias, Cout=Cc, out=out, ldo=Cc), next_gn, N * Ho * Wo)
+        kw = dict(src0=x, C0=Cc, N=N, Hs=H, Ws=W, up=0 if down else 1, stride=2 if down else 1, Ho=Ho, Wo=Wo, bias=conv.bias,
+                  Cout=Cc, out=out, ldo=Cc)
+        # Nearest-2x + 3x3 conv as four 2x2 convolutions over the source grid on pre-summed weights (up = 3: K = 4*C instead
+        # of 9*C).  Plans are inference only - the weights are frozen between two refresh_weights - and the training path
+        # (_backward.py) keeps up = 1: its gradients are defined on the 3x3 filter.  Stand-alone launches only: a conv that
+        # is a candidate stage of a persistent level chain (at most CHAIN_MAX_M output rows) keeps up = 1 whether or not the
+        # chains are enabled, so that a plan computes the same values either way.  LFVDM_CONV_NO_UP_PARITY (read by the
+        # library) or an unsupported shape: no candidates, the launch stays up = 1.
+        if not down and N * Ho * Wo > CHAIN_MAX_M:
+            codes = (C.c_int * 4)()     # (the query reads the shape only: any device tensor stands in for the pack)
+            if nat.lib().lfvdm_conv_igemm_candidates(C.byref(self.conv_args(**dict(kw, up=3, W=x))), codes, 4) > 0:
+                kw.update(up=3, W=self.packed_up2x(conv.weight))
+        if "W" not in kw:
+            kw["W"] = self.packed(conv.weight)
+        nact = self._final_conv(kw, next_gn, N * Ho * Wo)
         res = dict(parts=[(out, Cc)], H=Ho, W=Wo)
         if nact is not None:
             res["act1"] = nact
@@ -1239,6 +1261,9 @@ class Plan:
         s = nat.stream()
         L = nat.lib()
         for w, out, *part in self.packs:
+            if part == ["up2x"]:        # nearest-2x conv by parity class: the four 2x2 filters summed from the 3x3 one
+                nat.check(L.lfvdm_pack_conv_weight_up2x(_p(w), _p(out), w.shape[0], w.shape[1], s), "pack_up2x")
+                continue
             if part:        # input channels [c0, c1): a contiguous OIHW copy first (released in stream order)
                 w = w.detach()[:, part[0]:part[1]].contiguous()
             nat.check(L.lfvdm_pack_conv_weight(_p(w), _p(out), w.shape[0], w.shape[1], w.shape[2], s), "pack")

@@ -112,6 +112,7 @@ _SIGS = {
     "lfvdm_conv_igemm_config": ([C.POINTER(ConvArgs), C.POINTER(c_i), C.POINTER(c_i)], c_i),
     "lfvdm_conv_igemm_candidates": ([C.POINTER(ConvArgs), C.POINTER(c_i), c_i], c_i),
     "lfvdm_pack_conv_weight": ([c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
+    "lfvdm_pack_conv_weight_up2x": ([c_fp, c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_conv_wgrad": ([C.POINTER(ConvArgs), c_fp], c_i),
     "lfvdm_pack_conv_weight_t": ([c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_unpack_conv_grad": ([c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp], c_i),
@@ -598,6 +599,14 @@ def conv_igemm_struct(a):
 def pack_conv_weight(w, out):
     Cout, Cin, k, _ = w.shape
     check(lib().lfvdm_pack_conv_weight(ptr(w), ptr(out), Cout, Cin, k, stream()), "lfvdm_pack_conv_weight")
+
+
+def pack_conv_weight_up2x(w, out):
+    """OIHW 3x3 weight -> [4 classes][Cout][4 taps][Cin], the pre-summed pack of a nearest-2x conv run with up = 3."""
+    Cout, Cin, k, _ = w.shape
+    if k != 3 or out.numel() != 16 * Cout * Cin:
+        raise RuntimeError("lfvdm_pack_conv_weight_up2x needs a 3x3 weight and a [4][Cout][4][Cin] output")
+    check(lib().lfvdm_pack_conv_weight_up2x(ptr(w), ptr(out), Cout, Cin, stream()), "lfvdm_pack_conv_weight_up2x")
 
 
 def conv_in(x, x0, obs, w, bias, out, N, Cc, H, W, Cout):
