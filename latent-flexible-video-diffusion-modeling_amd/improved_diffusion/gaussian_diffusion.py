@@ -44,11 +44,13 @@ about 8e3 at t = 999 of the linear schedule, and would need folded tables and an
 """
 import enum
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch as th
 
 from . import _native as nat
+from ._replay import ReplayedStep, GraphSampler, BpdEvaluator  # noqa: F401  (their home is _replay; imported from here too)
 from .nn import mean_flat
 
 
@@ -94,6 +96,16 @@ class LossType(enum.Enum):
 
 def _bshape(t, ndim):
     return t.view(-1, *([1] * (ndim - 1)))
+
+
+class _Known(NamedTuple):
+    """The known region of one chain as ``GaussianDiffusion._chain`` takes it: ``known`` (the sample's shape) and ``mask``
+    (B, T, H, W), prepared on the chain's device; ``fixed``: one eps per chain (the deterministic rules); ``repeats``:
+    resample_steps."""
+    known: th.Tensor
+    mask: th.Tensor
+    fixed: bool
+    repeats: int
 
 
 LOSS_WEIGHTING_KINDS = ("none", "min_snr", "p2", "table")
@@ -534,19 +546,32 @@ class GaussianDiffusion:
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                       device=None, progress=False, latent_mask=None, return_attn_weights=False, return_decoded=True):
         """Full ancestral sampling chain (reference :403-471) -> (samples, attn-summary dict)."""
+        self._refuse_undecodable("p_sample_loop", return_decoded)
+        attns = {}
+        each = None
+        if return_attn_weights:
+            each = lambda neg_t, sample: self._accumulate_attn(attns, sample["attn"], self.num_timesteps - neg_t - 1, shape[0])
+        chain = self.p_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, latent_mask=latent_mask,
+            return_attn_weights=return_attn_weights, _reuse_buffers=True, _final_only=not return_attn_weights)
+        return self._final_sample(chain, return_decoded, each), attns
+
+    def _refuse_undecodable(self, loop, return_decoded):
+        """What every full-chain loop does first: nothing to decode with is found out before the chain, not behind it."""
         if return_decoded and not self.can_decode():
-            raise NotImplementedError("p_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); pass "
+            raise NotImplementedError(f"{loop}(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); pass "
                                       "return_decoded=False for latents - refused BEFORE the chain runs")
-        final, attns = None, {}
-        for neg_t, sample in enumerate(self.p_sample_loop_progressive(
-                model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                model_kwargs=model_kwargs, device=device, progress=progress, latent_mask=latent_mask,
-                return_attn_weights=return_attn_weights, _reuse_buffers=True, _final_only=not return_attn_weights)):
-            if return_attn_weights:
-                self._accumulate_attn(attns, sample["attn"], self.num_timesteps - neg_t - 1, shape[0])
-            final = sample
+
+    def _final_sample(self, chain, return_decoded, each=None):
+        """Drain a progressive generator (``each(step index, dict)`` sees every dict) -> a copy of the last ``sample``,
+        decoded or not."""
+        final = None
+        for n, final in enumerate(chain):
+            if each is not None:
+                each(n, final)
         out = final["sample"].clone()
-        return (self.decode(out) if return_decoded else out), attns
+        return self.decode(out) if return_decoded else out
 
     def _accumulate_attn(self, attns, attn_t, t, B):
         """Quartile-averaged attention maps for logging (reference :448-469)."""
@@ -575,45 +600,76 @@ class GaussianDiffusion:
         On the MI355X the step is one hipGraph replay (``GraphSampler``); yielded tensors are fresh
         copies unless the internal ``_reuse_buffers`` flag is set by ``p_sample_loop``.  Unlike the
         reference, grad mode is never left disabled when the generator is abandoned early."""
-        return self._sample_loop(("ancestral",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress,
-                                 return_attn_weights, _reuse_buffers, _final_only)
+        return self._chain(("ancestral",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress,
+                           return_attn_weights=return_attn_weights, _reuse_buffers=_reuse_buffers, _final_only=_final_only)
 
-    def _sample_loop(self, rule, model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress,
-                     return_attn_weights=False, _reuse_buffers=False, _final_only=False):
-        """The chain of any rule - ("ancestral",), ("ddim", eta) or ("dpmpp2m",) - behind the progressive loops; the dicts
-        of the ancestral chain carry ``attn`` as those of ``p_sample`` do."""
+    def _eager_step(self, rule, model, img, t, clip_denoised, denoised_fn, model_kwargs, prev, return_attn_weights=False):
+        """One step of ``rule`` through its public per-step method -> that method's dict.  ``prev``: the x0-hat of the step
+        before, the multistep rule's history."""
+        if rule[0] == "ancestral":
+            return self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                 return_attn_weights=return_attn_weights)
+        if rule[0] == "dpmpp2m":
+            return self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                          model_kwargs=model_kwargs, prev_pred_xstart=prev)
+        return self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                eta=rule[1])
+
+    def _chain(self, rule, model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress, *,
+               return_attn_weights=False, known=None, _reuse_buffers=False, _final_only=False):
+        """The chain of any rule - ("ancestral",), ("ddim", eta) or ("dpmpp2m",) - behind every progressive loop.  ``known``
+        (a ``_Known``): after every step the known part is put back at the level the step arrived at, and a timestep above
+        0 is taken ``repeats`` times with the state re-noised in between; None: a plain chain, which is that chain with no
+        blend and one repeat.  The dicts of the plain ancestral chain carry ``attn`` as those of ``p_sample`` do."""
         from .unet import UNetVideoModel
-        keys = ("sample", "pred_xstart", "attn") if rule[0] == "ancestral" else ("sample", "pred_xstart")
+        n = self.num_timesteps
+        keys = ("sample", "pred_xstart", "attn") if known is None and rule[0] == "ancestral" else ("sample", "pred_xstart")
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        indices = list(range(self.num_timesteps))[::-1]
+        img = noise if noise is not None else th.randn(*shape, device=device)      # torch's generator, before anything else
+        repeats, gen, eps = 1, None, None
+        if known is not None:      # a private generator (torch's own is not advanced): the fixed eps, the slow path's draws
+            repeats = known.repeats
+            gen = self._fork_generator(img.device)
+            eps = th.randn(*shape, device=img.device, generator=gen) if known.fixed else None
+        indices = list(range(n))[::-1]
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
         inner = getattr(model, "model", model)  # _WrappedModel -> module
         inner = getattr(inner, "module", inner)  # DDP -> module
-        fast = (isinstance(inner, UNetVideoModel) and img.is_cuda and denoised_fn is None
-                and not return_attn_weights and model_kwargs is not None)
-        if fast:
-            sampler = self._graph_sampler(inner, tuple(shape), clip_denoised, rule=rule)
-            sampler.begin(img, model_kwargs)
-            if _final_only and not progress:      # [p|ddim]_sample_loop: nobody looks at the intermediate states
-                out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
+        fast = isinstance(inner, UNetVideoModel) and img.is_cuda and denoised_fn is None and model_kwargs is not None
+        if fast and (known is not None or not return_attn_weights):
+            if known is None:
+                sampler, kw = self._graph_sampler(inner, tuple(shape), clip_denoised, rule=rule), {}
+            else:
+                sampler = self._known_region_sampler(inner, tuple(shape), clip_denoised, rule, known.fixed)
+                kw = dict(known=known.known, known_mask=known.mask, known_eps=eps)
+            sampler.begin(img, model_kwargs, **kw)
+            if _final_only and not progress and repeats == 1:      # the full-chain loops: nobody looks at the states between
+                out = sampler.run(n - 1, n)
                 if sampler.chain_timed_out():     # a persistent level chain gave up a wait: the samples are garbage
                     sampler.fall_back()           # (said on stderr) -> one launch per stage, and the chain again
-                    sampler.begin(img, model_kwargs)
-                    out = sampler.run(self.num_timesteps - 1, self.num_timesteps)
+                    sampler.begin(img, model_kwargs, **kw)
+                    out = sampler.run(n - 1, n)
                 yield {k: out[k] for k in keys}
                 return
-            for n, i in enumerate(indices):
-                out = sampler.step(i)
+            seed0 = sampler.seed.clone() if repeats > 1 else None
+            for m, i in enumerate(indices):
+                # host-driven resampling over the single-step graph: step (clock reset by step itself), re-noise, again
+                reps = repeats if i > 0 else 1
+                for r in range(reps):
+                    if seed0 is not None:
+                        th.add(seed0, self._repeat_seed_offset(r), out=sampler.seed)
+                    out = sampler.step(i)
+                    if r < reps - 1:
+                        sampler.renoise()
                 # a persistent level chain that gave up a wait leaves garbage behind and its abort word is sticky: every
                 # later step of this chain would abort as well.  The states already yielded cannot be taken back, so this
                 # path RAISES (checked every 64 steps and behind the last one; the final-only path above reruns the
                 # chain instead) - after switching the plan to one launch per stage, so that the caller's retry works
-                if (n & 63) == 63 or i == 0:
+                if (m & 63) == 63 or i == 0:
                     if sampler.chain_timed_out():
                         sampler.fall_back()
                         raise RuntimeError("a persistent level chain timed out during this sampling chain (lfvdm_level_chain): "
@@ -621,22 +677,47 @@ class GaussianDiffusion:
                                            "launch per stage - run the chain again")
                 yield {k: (out[k] if _reuse_buffers or out[k] is None else out[k].clone()) for k in keys}
             return
+        # the slow path: the per-step methods, then for a known region the same blend (the kernel on the GPU, plain torch on
+        # the CPU)
+        seed0 = None
+        if known is not None and img.is_cuda:      # the kernels' key; the CPU blend draws from ``gen`` itself
+            seed0 = th.empty(1, dtype=th.int64, device=img.device).random_(generator=gen)
         prev = None      # the multistep rule's history: the x0-hat of the step before
         for i in indices:
-            t = th.full((shape[0],), i, device=device, dtype=th.long)
-            with th.no_grad():
-                if rule[0] == "ancestral":
-                    out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                        model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
-                elif rule[0] == "dpmpp2m":
-                    out = self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                                 model_kwargs=model_kwargs, prev_pred_xstart=prev)
+            t = th.full((shape[0],), i, device=img.device, dtype=th.long)
+            reps = repeats if i > 0 else 1
+            for r in range(reps):
+                with th.no_grad():
+                    out = self._eager_step(rule, model, img, t, clip_denoised, denoised_fn, model_kwargs, prev, return_attn_weights)
                     prev = out["pred_xstart"]
-                else:
-                    out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                           model_kwargs=model_kwargs, eta=rule[1])
-            yield out
-            img = out["sample"]
+                    if known is not None:
+                        img = self._put_known_back(out["sample"], known, eps, t, gen,
+                                                   None if seed0 is None else seed0 + self._repeat_seed_offset(r), r < reps - 1)
+            if known is None:
+                yield out      # the per-step method's dict as it is
+                img = out["sample"]
+            else:
+                yield {"sample": img, "pred_xstart": out["pred_xstart"]}
+
+    def _put_known_back(self, sample, known, eps, t, gen, seed, renoise):
+        """The slow path's blend behind a step that consumed ``t`` -> the new state, a tensor of its own:
+        m (a[t] known + s[t] z) + (1 - m) sample, z the chain's fixed ``eps`` or a fresh draw, then with ``renoise`` one
+        forward step back up to level t.  On the GPU the two launches of the replayed step under the key ``seed``; on the
+        CPU plain torch drawing from ``gen``."""
+        tb = self.known_region_tables(sample.device)
+        img = sample.clone(memory_format=th.contiguous_format)
+        if img.is_cuda:
+            nat.known_blend(img, known.known, known.mask, t, tb["a"], tb["s"], eps=eps, seed=None if known.fixed else seed)
+            if renoise:
+                nat.renoise(img, t, tb["sqrt_1mbeta"], tb["sqrt_beta"], seed)
+            return img
+        m5 = known.mask.unsqueeze(2)
+        z = eps if known.fixed else th.randn(*img.shape, generator=gen)
+        v = _bshape(tb["a"][t], 5) * known.known + _bshape(tb["s"][t], 5) * z
+        img = th.where(m5 == 0, img, th.where(m5 == 1, v, m5 * v + (1 - m5) * img))
+        if renoise:
+            img = _bshape(tb["sqrt_1mbeta"][t], 5) * img + _bshape(tb["sqrt_beta"][t], 5) * th.randn(*img.shape, generator=gen)
+        return img
 
     # ------------------------------------------------------------------ DDIM (reference :524-685)
     def _ddim_step(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, reverse, noise=None):
@@ -670,22 +751,15 @@ class GaussianDiffusion:
         Extension: ``latent_mask`` and ``return_decoded`` are accepted and the final sample is treated as ``p_sample_loop``
         treats it (decoded unless ``return_decoded=False``; refused before the chain runs when there is nothing to decode
         with), so that the long-video sampler can call either loop.  The reference's DDIM loop returns the raw sample."""
-        if return_decoded and not self.can_decode():
-            raise NotImplementedError("ddim_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); pass "
-                                      "return_decoded=False for latents - refused BEFORE the chain runs")
-        final = None
-        for sample in self._sample_loop(("ddim", float(eta)), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
-                                        progress, _reuse_buffers=True, _final_only=True):
-            final = sample
-        out = final["sample"].clone()
-        return self.decode(out) if return_decoded else out
+        self._refuse_undecodable("ddim_sample_loop", return_decoded)
+        return self._final_sample(self._chain(("ddim", float(eta)), model, shape, noise, clip_denoised, denoised_fn, model_kwargs,
+                                              device, progress, _reuse_buffers=True, _final_only=True), return_decoded)
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                                      device=None, progress=False, eta=0.0):
         """Generator over the dicts of ``ddim_sample`` for t = T-1 .. 0 (reference :644-685); replayed through
         ``GraphSampler`` under the conditions of ``p_sample_loop_progressive``."""
-        return self._sample_loop(("ddim", float(eta)), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
-                                 progress)
+        return self._chain(("ddim", float(eta)), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress)
 
     # ------------------------------------------------------------------ DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2)
     def dpm_solver_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, prev_pred_xstart=None):
@@ -707,39 +781,37 @@ class GaussianDiffusion:
                                device=None, progress=False, latent_mask=None, return_decoded=True):
         """Full DPM-Solver++(2M) chain -> the final sample tensor alone; arguments and treatment of the final sample as
         ``ddim_sample_loop``'s, without ``eta`` (the rule is deterministic)."""
-        if return_decoded and not self.can_decode():
-            raise NotImplementedError("dpm_solver_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); "
-                                      "pass return_decoded=False for latents - refused BEFORE the chain runs")
-        final = None
-        for sample in self._sample_loop(("dpmpp2m",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
-                                        progress, _reuse_buffers=True, _final_only=True):
-            final = sample
-        out = final["sample"].clone()
-        return self.decode(out) if return_decoded else out
+        self._refuse_undecodable("dpm_solver_sample_loop", return_decoded)
+        return self._final_sample(self._chain(("dpmpp2m",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device,
+                                              progress, _reuse_buffers=True, _final_only=True), return_decoded)
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                            model_kwargs=None, device=None, progress=False):
         """Generator over the dicts of ``dpm_solver_sample`` for t = T-1 .. 0; replayed through ``GraphSampler`` under the
         conditions of ``p_sample_loop_progressive``."""
-        return self._sample_loop(("dpmpp2m",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress)
+        return self._chain(("dpmpp2m",), model, shape, noise, clip_denoised, denoised_fn, model_kwargs, device, progress)
+
+    def _cached_sampler(self, cache, key, unet, shape, clip_denoised, rule, known_fixed=None):
+        """The sampler under ``key`` of ``cache``, most recently used last; a new one when there is none or when the model's
+        engine is no longer the one it captured.  Graphs pin device memory: a cache keeps the few window shapes of a
+        long-video schedule (K, K-1, tail) - four samplers, whatever their rules: the limit bounds pinned memory, which does
+        not care about the rule, and a long-video run uses one rule throughout.  ``known_fixed`` not None: a known-region
+        sampler (``GraphSampler.enable_known_region``)."""
+        s = cache.pop(key, None)
+        if s is None or s.unet is not unet or s.engine is not unet.native_engine():
+            s = GraphSampler(self, unet, shape, clip_denoised, rule=rule)
+            if known_fixed is not None:
+                s.enable_known_region(known_fixed)
+            while len(cache) >= 4:
+                cache.pop(next(iter(cache)))
+        cache[key] = s
+        return s
 
     def _graph_sampler(self, unet, shape, clip_denoised, rule=("ancestral",)):
         # the update rule is part of the key (appended: position 1 stays the shape): a DDIM chain and an ancestral chain on
         # the same shape never share a captured graph
-        key = (id(unet), shape, bool(clip_denoised), tuple(rule))
-        s = self._samplers.get(key)
-        if s is None or s.unet is not unet or s.engine is not unet.native_engine():
-            s = GraphSampler(self, unet, shape, clip_denoised, rule=rule)
-            self._samplers.pop(key, None)
-            # graphs pin device memory: keep the few window shapes of a long-video schedule (K, K-1, tail).  DDIM samplers
-            # count against the SAME four: the limit bounds pinned memory, which does not care about the rule, and a
-            # long-video run uses one rule throughout
-            while len(self._samplers) >= 4:
-                self._samplers.pop(next(iter(self._samplers)))
-        else:
-            self._samplers.pop(key)           # re-insert: most recently used last
-        self._samplers[key] = s
-        return s
+        return self._cached_sampler(self._samplers, (id(unet), shape, bool(clip_denoised), tuple(rule)), unet, shape,
+                                    clip_denoised, rule)
 
     # ------------------------------------------------------------------ known-region sampling (RePaint; not in the reference)
     _KNOWN_RULES = {"ancestral": lambda eta: ("ancestral",), "ddim": lambda eta: ("ddim", float(eta)),
@@ -756,17 +828,10 @@ class GaussianDiffusion:
         return ((int(k) * cls._REPEAT_SEED_STRIDE + 2 ** 63) % 2 ** 64) - 2 ** 63
 
     def _known_region_sampler(self, unet, shape, clip_denoised, rule, fixed_noise):
-        """``_graph_sampler``'s twin for samplers whose captured step ends with the blend launch.  They live in a cache of
-        their own: the plain samplers, their graphs and their launch counts are what they were."""
-        key = (id(unet), shape, bool(clip_denoised), tuple(rule), "known")
-        s = self._known_samplers.pop(key, None)
-        if s is None or s.unet is not unet or s.engine is not unet.native_engine():
-            s = GraphSampler(self, unet, shape, clip_denoised, rule=rule)
-            s.enable_known_region(fixed_noise)
-            while len(self._known_samplers) >= 4:      # graphs pin device memory, as in _graph_sampler
-                self._known_samplers.pop(next(iter(self._known_samplers)))
-        self._known_samplers[key] = s
-        return s
+        """``_graph_sampler`` for samplers whose captured step ends with the blend launch.  They live in a cache of their
+        own: the plain samplers, their graphs and their launch counts are what they were."""
+        return self._cached_sampler(self._known_samplers, (id(unet), shape, bool(clip_denoised), tuple(rule), "known"), unet,
+                                    shape, clip_denoised, rule, known_fixed=bool(fixed_noise))
 
     @staticmethod
     def _fork_generator(device):
@@ -828,16 +893,10 @@ class GaussianDiffusion:
         (ancestral only): at every timestep above 0 the step is taken r times, the state re-noised by one forward step in
         between (RePaint's resampling with jump length 1), r U-Net forwards per timestep.  Everything else as in
         ``p_sample_loop`` / ``ddim_sample_loop`` / ``dpm_solver_sample_loop``; returns the final sample alone."""
-        if return_decoded and not self.can_decode():
-            raise NotImplementedError("known_region_sample_loop(return_decoded=True) needs the VAE (set_vae() / LFVDM_VAE_PATH); "
-                                      "pass return_decoded=False for latents - refused BEFORE the chain runs")
-        final = None
-        for sample in self._known_region_chain(model, shape, known, known_mask, sampler, eta, resample_steps, noise,
-                                               clip_denoised, denoised_fn, model_kwargs, latent_mask, device, progress,
-                                               _reuse_buffers=True, _final_only=True):
-            final = sample
-        out = final["sample"].clone()
-        return self.decode(out) if return_decoded else out
+        self._refuse_undecodable("known_region_sample_loop", return_decoded)
+        return self._final_sample(self._known_region_chain(model, shape, known, known_mask, sampler, eta, resample_steps, noise,
+                                                           clip_denoised, denoised_fn, model_kwargs, latent_mask, device, progress,
+                                                           _reuse_buffers=True, _final_only=True), return_decoded)
 
     def known_region_sample_loop_progressive(self, model, shape, known, known_mask, *, sampler="ancestral", eta=0.0,
                                              resample_steps=1, noise=None, clip_denoised=True, denoised_fn=None,
@@ -857,84 +916,9 @@ class GaussianDiffusion:
         mask = known_mask.to(device=device, dtype=th.float32).broadcast_to(B, T, H, W)
         if latent_mask is not None:      # once, on the host side of the chain: frames that are not latent are never blended
             mask = mask * latent_mask.to(device=device, dtype=th.float32).reshape(B, T, 1, 1)
-        return self._known_region_steps(rule, fixed, repeats, model, tuple(shape), known, mask.contiguous(), noise, clip_denoised,
-                                        denoised_fn, model_kwargs, device, progress, _reuse_buffers, _final_only)
-
-    def _known_region_steps(self, rule, fixed, repeats, model, shape, known, mask, noise, clip_denoised, denoised_fn,
-                            model_kwargs, device, progress, _reuse_buffers, _final_only):
-        from .unet import UNetVideoModel
-        n = self.num_timesteps
-        img = noise if noise is not None else th.randn(*shape, device=device)      # torch's generator: as the plain loops
-        gen = self._fork_generator(img.device)
-        eps = th.randn(*shape, device=img.device, generator=gen) if fixed else None
-        indices = list(range(n))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        inner = getattr(model, "model", model)
-        inner = getattr(inner, "module", inner)
-        if isinstance(inner, UNetVideoModel) and img.is_cuda and denoised_fn is None and model_kwargs is not None:
-            s = self._known_region_sampler(inner, shape, clip_denoised, rule, fixed)
-            s.begin(img, model_kwargs, known=known, known_mask=mask, known_eps=eps)
-            if repeats == 1 and _final_only and not progress:
-                out = s.run(n - 1, n)
-                if s.chain_timed_out():      # the plain loops' protocol (_sample_loop)
-                    s.fall_back()
-                    s.begin(img, model_kwargs, known=known, known_mask=mask, known_eps=eps)
-                    out = s.run(n - 1, n)
-                yield {k: out[k] for k in ("sample", "pred_xstart")}
-                return
-            seed0 = s.seed.clone() if repeats > 1 else None
-            for m, i in enumerate(indices):
-                # host-driven resampling over the single-step graph: step (clock reset by step itself), re-noise, again
-                reps = repeats if i > 0 else 1
-                for k in range(reps):
-                    if seed0 is not None:
-                        th.add(seed0, self._repeat_seed_offset(k), out=s.seed)
-                    out = s.step(i)
-                    if k < reps - 1:
-                        s.renoise()
-                if (m & 63) == 63 or i == 0:
-                    if s.chain_timed_out():
-                        s.fall_back()
-                        raise RuntimeError("a persistent level chain timed out during this sampling chain (lfvdm_level_chain): "
-                                           "the states yielded since the last check are not valid; the plan now runs one "
-                                           "launch per stage - run the chain again")
-                yield {k: (out[k] if _reuse_buffers else out[k].clone()) for k in ("sample", "pred_xstart")}
-            return
-        # the slow path: the per-step methods, then the same blend (the kernel on the GPU, plain torch on the CPU)
-        tb = self.known_region_tables(img.device)
-        seed0 = th.empty(1, dtype=th.int64, device=img.device).random_(generator=gen) if img.is_cuda else None
-        m5 = mask.unsqueeze(2)
-        prev = None
-        for i in indices:
-            t = th.full((shape[0],), i, device=img.device, dtype=th.long)
-            reps = repeats if i > 0 else 1
-            for k in range(reps):
-                with th.no_grad():
-                    if rule[0] == "ancestral":
-                        out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                            model_kwargs=model_kwargs)
-                    elif rule[0] == "dpmpp2m":
-                        out = self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                                     model_kwargs=model_kwargs, prev_pred_xstart=prev)
-                        prev = out["pred_xstart"]
-                    else:
-                        out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                               model_kwargs=model_kwargs, eta=rule[1])
-                    img = out["sample"].clone(memory_format=th.contiguous_format)
-                    if img.is_cuda:
-                        seed = seed0 + self._repeat_seed_offset(k)
-                        nat.known_blend(img, known, mask, t, tb["a"], tb["s"], eps=eps, seed=None if fixed else seed)
-                        if k < reps - 1:
-                            nat.renoise(img, t, tb["sqrt_1mbeta"], tb["sqrt_beta"], seed)
-                    else:
-                        z = eps if fixed else th.randn(*shape, generator=gen)
-                        v = _bshape(tb["a"][t], 5) * known + _bshape(tb["s"][t], 5) * z
-                        img = th.where(m5 == 0, img, th.where(m5 == 1, v, m5 * v + (1 - m5) * img))
-                        if k < reps - 1:
-                            img = _bshape(tb["sqrt_1mbeta"][t], 5) * img + _bshape(tb["sqrt_beta"][t], 5) * th.randn(*shape, generator=gen)
-            yield {"sample": img, "pred_xstart": out["pred_xstart"]}
+        return self._chain(rule, model, tuple(shape), noise, clip_denoised, denoised_fn, model_kwargs, device, progress,
+                           known=_Known(known, mask.contiguous(), fixed, repeats), _reuse_buffers=_reuse_buffers,
+                           _final_only=_final_only)
 
     def model_timestep_table(self, device):
         """Per-step model timestep (float) — identity/rescale here, remap in SpacedDiffusion."""
@@ -1188,381 +1172,6 @@ class GaussianDiffusion:
         z = video.flatten(0, 1).to(self.enc_dec_dtype).to(self._vae_device(video.device))
         frames = th.cat([self.vae.decode(z[i:i + chunk_size], num_frames=1).sample for i in range(0, z.shape[0], chunk_size)])
         return frames.unflatten(0, (B, T)).to(video.device).to(out_dtype)
-
-
-class ReplayedStep:
-    """One step of a chain over a private plan, captured as a hipGraph over the plan's static buffers: what the sampler and
-    the bits-per-dim evaluator share.  The plan and its timestep tables, the device-side clock ``t_buf``, the per-chain
-    table build, the warm-up and capture of ``_step_body`` (the subclass's), the chain-timeout check and the fall-back,
-    and ``step``: a single replay."""
-
-    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise):
-        # inject_noise (parity tests): the replayed step READS ``self.noise`` - the caller fills it before every
-        # ``step`` - instead of drawing it (the reference's th.randn_like, gaussian_diffusion.py:396)
-        self.diffusion, self.unet, self.shape = diffusion, unet, tuple(shape)
-        self.clip = bool(clip_denoised)
-        self.inject_noise = bool(inject_noise)
-        diffusion._check_native_modes()
-        # the mean type is fixed for the life of the captured graphs (the caches live on the diffusion object: they need
-        # no key element).  Not to be confused with model_kwargs["x0"], the conditioning frames
-        self.x0_mode = diffusion.predicts_xstart
-        B, T, Cx, H, W = self.shape
-        from ._engine import Plan
-        # a private plan: the chain's state lives in its static buffers, so it must not be shared
-        # with eager model() calls on the same shape
-        self.engine = unet.native_engine()
-        # the chain walks a known schedule: everything that depends on (t, frame_indices) alone is tabulated once per
-        # chain (Plan.build_time_tables / build_R_tables) instead of being recomputed by four launches in every step
-        self.plan = Plan(self.engine, B, T, H, W, False, time_steps=diffusion.num_timesteps)
-        self.plan.refresh_weights()
-        dev = self.plan.dev
-        self.tb = diffusion.tables(dev)
-        self.ts_table = diffusion.model_timestep_table(dev)
-        self.t_buf = self.plan.t_sel if self.plan.time_steps else th.zeros(B, dtype=th.int64, device=dev)
-        self._table_events = None      # (start, end) events around the table build of the last begin()
-        self._ts_key = tuple(self.ts_table.tolist())
-        self.graph = None
-        self.expected_t = None
-        self._abort_unchecked = False       # steps have run since the chains' abort words were last read
-        self.chain_timeouts = 0
-
-    @property
-    def table_build_ms(self):
-        """GPU time of the table build of the last ``begin()`` (synchronises on its end event when read)."""
-        if self._table_events is None:
-            return 0.0
-        e0, e1 = self._table_events
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
-    def _build_chain_tables(self, frame_indices):
-        """Once per chain, plan with timestep tables: the FiLM rows (once per set of weights), this window's R tables, the
-        block the chain starts in; then the clock is put on the first timestep, so that the tuning / warm-up launches
-        find valid FiLM rows.  Shared by every replayed-step class over a private plan."""
-        pl, n = self.plan, self.diffusion.num_timesteps
-        if not pl.time_steps:
-            return
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        if pl.tables_sig != (pl.time_signature(), self._ts_key):
-            pl.build_time_tables(self.ts_table)          # once per set of weights
-        pl.build_R_tables(frame_indices)                 # once per chain: R depends on this window's frames
-        pl.ensure_R(n - 1)                               # (rolling window: the block the chain starts in)
-        e1.record()
-        self._table_events = (e0, e1)        # read lazily (table_build_ms): no host stall between windows / chains
-        self.t_buf.fill_(n)
-        pl.tick(self.t_buf, self.ts_table)
-
-    def _capture_step(self):
-        """Tune the plan (once), warm ``_step_body`` up on a side stream and capture it as ``self.graph``.  The plan's
-        input is saved and restored around it, and so is the caller's RNG stream: building the graph draws warm-up noise,
-        and a seed must give the same result whether or not this shape was seen before."""
-        import os
-        pl = self.plan
-        rng_state = th.cuda.get_rng_state(pl.dev)
-        if os.environ.get("LFVDM_AUTOTUNE", "1") != "0" and not getattr(pl, "tuned", False):
-            saved0 = pl.x_in.clone()
-            pl.launch()               # realistic operand contents for the timing runs
-            pl.autotune()
-            pl.x_in.copy_(saved0)
-        # warm-up on a side stream (sets kernel attributes, fills caches), then capture
-        saved = pl.x_in.clone()
-        self.t_buf.fill_(self.diffusion.num_timesteps)
-        s = th.cuda.Stream()
-        s.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(s):
-            self._step_body()
-        th.cuda.current_stream().wait_stream(s)
-        g = th.cuda.CUDAGraph()
-        # thread-local capture: a process group's watchdog thread may query events while this thread captures
-        with th.cuda.graph(g, capture_error_mode="thread_local"):
-            self._step_body()
-        self.graph = g
-        pl.x_in.copy_(saved)
-        th.cuda.synchronize()
-        th.cuda.set_rng_state(rng_state, pl.dev)
-
-    def _begin_chain(self, x, model_kwargs):
-        """``x`` becomes the plan's input; this chain's tables; the graph (first chain only); the clock on the top."""
-        pl = self.plan
-        if pl._sig != pl.weight_signature():
-            pl.refresh_weights()  # parameters changed since the last chain
-        with th.no_grad():
-            pl.set_inputs(x, model_kwargs["x0"], th.zeros(pl.B, device=pl.dev), model_kwargs["frame_indices"],
-                          model_kwargs["obs_mask"], model_kwargs["latent_mask"])
-            self._build_chain_tables(model_kwargs["frame_indices"])
-            if self.graph is None:
-                self._capture_step()
-            self.t_buf.fill_(self.diffusion.num_timesteps)     # the step pre-decrements
-        self.expected_t = self.diffusion.num_timesteps - 1
-
-    def chain_timed_out(self):
-        """Did a wait inside one of the plan's persistent level chains give up (LFVDM_CHAIN_TIMEOUT_S)?  Synchronises (one
-        read-back for all chains of the plan)."""
-        self._abort_unchecked = False
-        return bool(self.plan.chains) and self.plan.chains_aborted()
-
-    def fall_back(self):
-        """After a chain timeout: the results of the chain that just ran are not to be trusted.  Say so, run this plan one
-        launch per stage from now on, and have the step graph captured again."""
-        import sys
-        print("[lfvdm] ERROR: a persistent level chain timed out (lfvdm_level_chain); falling back to the per-launch plan",
-              file=sys.stderr, flush=True)
-        self.plan.disable_chains()
-        self.graph = None
-        self.chain_timeouts += 1
-
-    def step(self, i):
-        if i != self.expected_t:  # arbitrary order requested: reset the device-side counter
-            self.t_buf.fill_(i + 1)
-        self.plan.ensure_R(i)
-        self.graph.replay()
-        self._abort_unchecked = True
-        self.expected_t = max(i - 1, 0)
-
-
-class GraphSampler(ReplayedStep):
-    """One denoising step (timestep remap -> U-Net forward -> noise -> x_{t-1} update -> t -= 1)
-    captured as a hipGraph over the engine's static buffers; ``step`` is a single replay."""
-
-    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False, rule=("ancestral",)):
-        # rule: ("ancestral",), ("ddim", eta) or ("dpmpp2m",) - which update closes the step; fixed for the life of the
-        # captured graphs
-        self.rule = tuple(rule)
-        if self.rule[0] not in ("ancestral", "ddim", "dpmpp2m") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
-            raise ValueError(f"unknown update rule {rule!r}")
-        super().__init__(diffusion, unet, shape, clip_denoised, inject_noise)
-        dev = self.plan.dev
-        # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic) or k1 / k2 / k3 of the multistep rule,
-        # and what the update is launched with
-        self.multistep = self.rule[0] == "dpmpp2m"
-        if self.multistep:
-            self.ddim = diffusion.dpm_solver_tables(dev)
-        else:
-            self.ddim = diffusion.ddim_tables(dev, self.rule[1]) if self.rule[0] == "ddim" else None
-        self.update = diffusion._update_args(dev, self.rule)
-        self.noise = th.empty(self.shape, device=dev)
-        # the step's x0-hat; under the multistep rule also the history the next step reads (in and out of one launch)
-        self.pred = th.empty(self.shape, device=dev)
-        # the replayed step draws its noise inside the update kernel (lfvdm_update_rng_x0: Philox keyed by a per-chain seed
-        # that begin() takes from torch's generator, so th.manual_seed still fixes the video); LFVDM_SAMPLER_NOISE=torch
-        # keeps the th.randn launch
-        self.seed = th.zeros(1, dtype=th.int64, device=dev)
-        # consecutive steps of a chain are also captured K at a time (``run``): a graph launch costs the GPU ~18 us whatever
-        # it holds (1063 -> 1080 steps/s at cfg B with 8 steps per launch; 32 and more lose again); LFVDM_STEPS_PER_GRAPH=1: off
-        import os
-        self.K = max(1, int(os.environ.get("LFVDM_STEPS_PER_GRAPH", "8")))
-        if self.plan.time_steps and self.plan.time_ring:
-            self.K = min(self.K, self.plan.time_ring // 2)     # a graph launch must not walk more than half the R ring
-        self.graph_k = None
-        # known-region sampling (``enable_known_region``): static buffers the captured step's last launch reads
-        self.known = self.known_mask = self.known_eps = self.known_noise = self.known_tb = None
-
-    def enable_known_region(self, fixed_noise, record_noise=False):
-        """Make this a known-region sampler, before its first chain: the captured step then ENDS with the blend launch
-        (lfvdm_known_blend) over the static buffers ``known`` (the state's shape), ``known_mask`` (B, T, H, W) and - with
-        ``fixed_noise``, the deterministic rules - ``known_eps``; ``begin`` refills them, so every chain replays the same
-        graphs.  Without ``fixed_noise`` the blend draws fresh noise under the chain's ``seed`` (its own Philox stream);
-        ``record_noise`` keeps what it drew in ``known_noise`` (tests)."""
-        if self.graph is not None or self.graph_k is not None:
-            raise RuntimeError("enable_known_region comes before the sampler's first chain: its graphs are captured already")
-        B, T, _, H, W = self.shape
-        dev = self.plan.dev
-        self.known_tb = self.diffusion.known_region_tables(dev)
-        self.known = th.zeros(self.shape, device=dev)
-        self.known_mask = th.zeros(B, T, H, W, device=dev)
-        self.known_eps = th.zeros(self.shape, device=dev) if fixed_noise else None
-        self.known_noise = th.zeros(self.shape, device=dev) if record_noise and not fixed_noise else None
-
-    def _step_body(self):
-        """The denoising step; a known-region sampler then puts the known part back at the level the step arrived at
-        (``t_buf`` still holds the timestep the step consumed)."""
-        self._denoise_body()
-        if self.known is not None:
-            nat.known_blend(self.plan.x_in, self.known, self.known_mask, self.t_buf, self.known_tb["a"], self.known_tb["s"],
-                            eps=self.known_eps, seed=self.seed, noise_out=self.known_noise)
-            self.extra_launches += 1
-
-    def renoise(self):
-        """Resampling: the state one forward step back up, to the level of the timestep the last step consumed (the clock
-        still holds it), with fresh noise under the chain's seed (lfvdm_renoise: a Philox stream of its own).  One eager
-        launch between replays; the next ``step`` of the same timestep puts the clock back."""
-        tb = self.diffusion.known_region_tables(self.plan.dev)
-        nat.renoise(self.plan.x_in, self.t_buf, tb["sqrt_1mbeta"], tb["sqrt_beta"], self.seed)
-
-    def _denoise_body(self):
-        """The clock and the forward, then at most one update launch, chosen by where the noise comes from."""
-        import os
-        pl = self.plan
-        recip, recipm1, c1, c2, sg, rule, mean_type = self.update
-        # DDIM with eta = 0 and the multistep rule (sg is its k3): no noise of any kind, whatever the noise settings say
-        det = sg is None or self.multistep
-        in_kernel = det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
-        # the x_{t-1} update rides in the plan's last launch (output conv + update: lfvdm_conv_out_update_x0) where the
-        # shape allows; LFVDM_FUSED_HEAD=0 keeps the two launches (A/B aid)
-        fused = (os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
-                 and pl.fuse_head_update(self.t_buf, self.tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
-                                         ddim=self.ddim, predict_xstart=self.x0_mode))
-        # device-side clock: t <- max(t - 1, 0), model timestep <- table[t]  (t_buf holds "previous t"); with timestep
-        # tables it also fetches the FiLM rows of the new t, and rides in the first launch of the forward
-        tick_in_conv = bool(pl.time_steps) and os.environ.get("LFVDM_TICK_IN_CONV", "1") != "0"
-        if tick_in_conv:
-            pl.launch(tick=(self.t_buf, self.ts_table))
-        else:
-            pl.tick(self.t_buf, self.ts_table)
-            pl.launch()
-        draw = not (fused or in_kernel or self.inject_noise)
-        # launches of a step beside the plan's own (bench.py reports launches per step): the clock, the update, the draw
-        self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw)
-        if fused:
-            return
-        if self.multistep:
-            nat.update_ms_x0(pl.x_in, pl.out, self.pred, self.t_buf, recip, recipm1, c1, c2, sg, mean_type, self.clip, pl.x_in,
-                             self.pred)
-            return
-        if in_kernel:
-            nat.update_rng_x0(pl.x_in, pl.out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
-                              mean_type, self.clip, pl.x_in, None if det else self.seed, self.pred)
-            return
-        if draw:
-            self.noise.normal_()
-        nat.update_x0(pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, self.clip, pl.x_in,
-                      self.pred)
-
-    def begin(self, img, model_kwargs, known=None, known_mask=None, known_eps=None):
-        # callers that drive step() / run() themselves: checked once per chain, here - unless whoever ran the previous
-        # chain has looked already (p_sample_loop does, behind run(): one host synchronisation per chain, not two)
-        if self._abort_unchecked and self.chain_timed_out():
-            self.fall_back()
-        if (self.known is None) != (known is None) or (self.known_eps is None) != (known_eps is None):
-            raise ValueError("known / known_mask (and known_eps under a fixed-noise rule) go to a sampler made with "
-                             "enable_known_region, and to no other")
-        if known is not None:      # this chain's known region -> the static buffers (no draw from torch's generator)
-            self.known.copy_(known)
-            self.known_mask.copy_(known_mask)
-            if known_eps is not None:
-                self.known_eps.copy_(known_eps)
-        self._begin_chain(img, model_kwargs)
-        self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
-        if self.multistep:
-            self.pred.zero_()                               # no history (k3 = 0 at the chain's first step: it is not read)
-
-    def fall_back(self):
-        super().fall_back()
-        self.graph_k = None
-
-    def chain_table_ms(self):
-        """GPU milliseconds of ALL table building of one chain of this sampler (every R block once; the FiLM rows are per
-        set of weights and not included): with the rolling window the refills ride between the graph launches of ``run``,
-        this measures them on their own (synchronises)."""
-        pl = self.plan
-        if not pl.time_steps:
-            return 0.0
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        th.cuda.synchronize()
-        e0.record()
-        pl.fill_whole_chain()
-        e1.record()
-        e1.synchronize()
-        if self.expected_t is not None:
-            pl.ensure_R(self.expected_t)
-        return e0.elapsed_time(e1)
-
-    def _state(self):
-        return {"sample": self.plan.x_in, "pred_xstart": self.pred, "attn": None}
-
-    def _check_order(self, i):
-        """A multistep chain walks consecutive timesteps (its history is the step before); n - 1 starts a chain over."""
-        if self.multistep and i != self.expected_t and i != self.diffusion.num_timesteps - 1:
-            raise ValueError(f"the multistep rule {self.rule!r} walks consecutive timesteps: expected t = {self.expected_t} "
-                             f"(or {self.diffusion.num_timesteps - 1}, a new chain), got {i}")
-
-    def step(self, i):
-        self._check_order(i)
-        super().step(i)
-        return self._state()
-
-    def run(self, i, n):
-        """``n`` consecutive steps t = i, i-1, ... (the clock stops at 0): exactly ``step`` n times - the noise is keyed by
-        (chain seed, t, element), the clock lives on the device - but K steps per graph launch while at least K remain."""
-        if self.inject_noise and n > 1:
-            raise ValueError("inject_noise: the caller provides the noise of every step - use step()")
-        self._check_order(i)
-        if i != self.expected_t:
-            self.t_buf.fill_(i + 1)
-        left, t = int(n), int(i)
-        if self.K > 1 and left >= self.K:
-            if self.graph_k is None:
-                g = th.cuda.CUDAGraph()
-                th.cuda.synchronize()
-                with th.no_grad(), th.cuda.graph(g, capture_error_mode="thread_local"):
-                    for _ in range(self.K):
-                        self._step_body()
-                self.graph_k = g
-            while left >= self.K:
-                self.plan.ensure_R(t, t - self.K + 1)      # rolling R window: the timesteps this launch walks
-                self.graph_k.replay()
-                left -= self.K
-                t = max(t - self.K, 0)
-        for _ in range(left):
-            self.plan.ensure_R(t)
-            self.graph.replay()
-            t = max(t - 1, 0)
-        self._abort_unchecked = True
-        self.expected_t = max(int(i) - int(n), 0)
-        return self._state()
-
-
-class BpdEvaluator(ReplayedStep):
-    """One evaluation step of ``calc_bpd_loop`` (clock tick -> noise draw -> q_sample into the plan's input -> U-Net forward
-    -> lfvdm_vb_terms into column j of the (N, T) results) captured as a hipGraph over a private plan with timestep
-    tables; ``step(i)`` - a single replay - writes the term of timestep ``i`` to column num_timesteps - 1 - i of ``vb`` /
-    ``xstart_mse`` / ``mse``: the column index is derived on the device from the clock."""
-
-    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise=False):
-        super().__init__(diffusion, unet, shape, clip_denoised, inject_noise)
-        # the evaluator always walks with timestep tables (the sampler also serves plans without them)
-        assert self.plan.time_steps == diffusion.num_timesteps and self.plan.t_sel is not None
-        B, T, n, dev = self.plan.B, self.plan.T, diffusion.num_timesteps, self.plan.dev
-        self.x_start = th.empty(self.shape, device=dev)
-        self.noise = th.empty(self.shape, device=dev)
-        self.mask = th.ones(B, T, device=dev)
-        self.vb, self.xstart_mse, self.mse = (th.zeros(B, n, device=dev) for _ in range(3))
-
-    def _step_body(self):
-        pl, tb, d = self.plan, self.tb, self.diffusion
-        pl.tick(self.t_buf, self.ts_table)          # t <- max(t - 1, 0), model timestep and FiLM rows of the new t
-        if not self.inject_noise:
-            self.noise.normal_()                    # torch's graph-safe generator (th.manual_seed fixes the evaluation)
-        nat.q_sample(self.x_start, self.noise, self.t_buf, tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"], pl.x_in)
-        pl.launch()
-        recip, recipm1, c1, c2, post_lv, model_lv = d._vb_tables(pl.dev)
-        nat.vb_terms(self.x_start, pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, c1, c2, post_lv, model_lv, self.mask,
-                     nat.MEAN_X0 if self.x0_mode else nat.MEAN_EPS, self.clip, self.vb, self.xstart_mse, self.mse, None,
-                     col_base=d.num_timesteps - 1)
-
-    def begin(self, x_start, model_kwargs, latent_mask=None):
-        with th.no_grad():
-            self.x_start.copy_(x_start)
-            if latent_mask is None:
-                self.mask.fill_(1.0)
-            else:
-                self.mask.copy_(latent_mask.reshape(self.mask.shape))
-        self._begin_chain(self.x_start, model_kwargs)
-
-    def evaluate(self, x_start, model_kwargs, latent_mask=None):
-        """Every timestep, descending -> fresh (N, T) copies of vb, xstart_mse, mse.  A persistent level chain that gave
-        up a wait leaves garbage behind: the walk is then run again, one launch per stage (the samplers' protocol)."""
-        n = self.diffusion.num_timesteps
-        for attempt in range(2):
-            self.begin(x_start, model_kwargs, latent_mask)
-            for i in range(n - 1, -1, -1):
-                self.step(i)
-            if attempt == 0 and self.chain_timed_out():
-                self.fall_back()
-                continue
-            break
-        return self.vb.clone(), self.xstart_mse.clone(), self.mse.clone()
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

@@ -181,6 +181,75 @@ def test_cpu_chain_with_an_empty_mask_is_the_plain_loop():
     assert torch.equal(got, want)
 
 
+def state_net(x, timesteps=None, **kw):
+    """A stand-in whose output depends on the state (``net`` predicts zero noise whatever it is fed, which hides a step that
+    was given the wrong state or taken in the wrong order)."""
+    return 0.3 * x, None
+
+
+# sampler= / eta= of the known-region loop, and the plain loop of the same rule with its per-step method and key set
+CHAINS = {
+    "ancestral": ("ancestral", {}, "p_sample_loop", "p_sample", {"sample", "pred_xstart", "attn"}),
+    "ddim_eta0": ("ddim", {"eta": 0.0}, "ddim_sample_loop", "ddim_sample", {"sample", "pred_xstart"}),
+    "ddim_eta1": ("ddim", {"eta": 1.0}, "ddim_sample_loop", "ddim_sample", {"sample", "pred_xstart"}),
+    "dpm_solver": ("dpm_solver", {}, "dpm_solver_sample_loop", "dpm_solver_sample", {"sample", "pred_xstart"}),
+}
+CPU_KW = dict(denoised_fn=identity, model_kwargs={}, device="cpu")
+
+
+def plain_final(diff, loop, kw):
+    out = getattr(diff, loop)(state_net, SHAPE, return_decoded=False, **kw, **CPU_KW)
+    return out[0] if loop == "p_sample_loop" else out
+
+
+@pytest.mark.parametrize("chain", sorted(CHAINS))
+def test_cpu_chain_with_an_empty_mask_is_the_plain_loop_of_every_sampler(chain):
+    sampler, kw, loop, _, _ = CHAINS[chain]
+    diff = make_diffusion("10")
+    known, empty = torch.full(SHAPE, 7.0), torch.zeros(2, 3, 4, 4)
+    torch.manual_seed(11)
+    want = plain_final(diff, loop, kw)
+    assert bool(torch.isfinite(want).all())
+    torch.manual_seed(11)
+    got = diff.known_region_sample_loop(state_net, SHAPE, known, empty, sampler=sampler, return_decoded=False, **kw, **CPU_KW)
+    assert torch.equal(got, want)
+    torch.manual_seed(11)
+    last = list(diff.known_region_sample_loop_progressive(state_net, SHAPE, known, empty, sampler=sampler, **kw, **CPU_KW))[-1]
+    assert torch.equal(last["sample"], want)
+
+
+@pytest.mark.parametrize("chain", sorted(CHAINS))
+def test_each_plain_loop_is_its_per_step_method_by_hand(chain):
+    """The slow path's contract, whatever drives it: the start noise first, then the public per-step method for
+    t = n-1 .. 0 on the sample of the step before, the multistep rule fed the x0-hat of the step before."""
+    _, kw, loop, step, keys = CHAINS[chain]
+    diff = make_diffusion("10")
+    n = diff.num_timesteps
+    torch.manual_seed(13)
+    x, prev = torch.randn(*SHAPE), None
+    for i in range(n - 1, -1, -1):
+        t = torch.full((SHAPE[0],), i, dtype=torch.long)
+        more = {"prev_pred_xstart": prev} if step == "dpm_solver_sample" else kw
+        with torch.no_grad():
+            out = getattr(diff, step)(state_net, x, t, clip_denoised=True, denoised_fn=identity, model_kwargs={}, **more)
+        x, prev = out["sample"], out["pred_xstart"]
+    assert bool(torch.isfinite(x).all())
+    torch.manual_seed(13)
+    assert torch.equal(plain_final(diff, loop, kw), x)
+    torch.manual_seed(13)
+    outs = list(getattr(diff, loop + "_progressive")(state_net, SHAPE, **kw, **CPU_KW))
+    assert len(outs) == n and all(set(o) == keys for o in outs)
+    assert torch.equal(outs[-1]["sample"], x) and torch.equal(outs[-1]["pred_xstart"], prev)
+
+
+def test_the_chain_driver_and_its_timeout_text_exist_once():
+    from improved_diffusion.gaussian_diffusion import GaussianDiffusion
+    src = inspect.getsource(GaussianDiffusion)
+    assert src.count("the states yielded since the last check are not valid") == 1
+    assert not hasattr(GaussianDiffusion, "_known_region_steps") and not hasattr(GaussianDiffusion, "_sample_loop")
+    assert inspect.isgeneratorfunction(GaussianDiffusion._chain)
+
+
 def test_cpu_chain_blends_per_frame_and_per_pixel():
     """Left half known on the frames the latent mask names: exactly known there, the plain chain's values elsewhere are
     NOT reproduced (the model sees the blended state), but stay finite; the forward count under resampling is r (n-1) + 1."""
