@@ -766,6 +766,41 @@ int lfvdm_adamw_ema_clip(const lfvdm_adamw_args* a, const float* stat, void* str
 int lfvdm_prepare_batch(const float* pool, const int32_t* table, float* batch, int64_t* frame_indices, float* obs_mask,
                         float* latent_mask, int B, int F, int Tp, int frame_elems, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Search for optimised conditioning frames (improved_diffusion/optimal_schedule.py; not in the reference).  One pass scores
+ * G candidate conditioning sets on V videos as W = G * V windows of K slots; window w shows video w % V.
+ *   table [W][K] int32   the video frame a slot shows, -1: padding        role [W][K] int32   LFVDM_SLOT_*
+ * lfvdm_search_assemble: from the resident pool [V][Tv][frame_elems] write x0 and x_start [W][K][frame_elems] (the same
+ *   gathered frames; padding slots zero), obs_mask / latent_mask / mask [W][K] fp32 (mask = observed or latent) and
+ *   frame_indices [W][K] int64 (0 in padding slots).  A frame index outside [0, Tv) makes the slot padding.
+ * lfvdm_search_noise_qsample: the head of the replayed evaluation step; what changes between replays is read from device
+ *   memory.  ctl (int32 [4]): ctl[0] the position j (clamped into [0, n_t)), ctl[1] an arrival ticket, ctl[2] = n_t; key
+ *   (int64 [2]): the seed and the window step.  t = t_list[j] (int64, entries must index the two tables): t_buf[w] <- t + 1
+ *   for the plan's clock, which pre-decrements; noise and x_t = sqrt_acp[t] x_start + sqrt_1macp[t] noise over
+ *   [W][K][frame_elems] (padding slots zero); then ctl[0] <- j + 1 by the last workgroup to finish (ctl[0] and ctl[1] are zero
+ *   before a pass).
+ *   Noise: Philox4x32-10 under the key `seed`, counter (quad in the frame, video frame index, j << 16 | video,
+ *   step << 8 | 3) - a function of (seed, step, j, video, video frame, element), whatever slot or window holds the frame.
+ * lfvdm_search_noise_fill: the same noise for the position j given as an argument, nothing else written.
+ * lfvdm_search_scores: scores[g] = mean over v < V, j < n_t of terms[(g * V + v) * ld + col], col = col_base - t_list[j]
+ *   (the column lfvdm_vb_terms wrote) or j for col_base < 0; added in double in that order by one thread: bitwise
+ *   reproducible, no atomics.
+ * frame_elems a multiple of 4, buffers 16-byte aligned, W, V, n_t <= 65535, step < 2^24; else LFVDM_E_SHAPE.
+ * ------------------------------------------------------------------------------------- */
+#define LFVDM_SLOT_PAD 0
+#define LFVDM_SLOT_OBS 1
+#define LFVDM_SLOT_LATENT 2
+int lfvdm_search_assemble(const float* pool, const int32_t* table, const int32_t* role, float* x0, float* x_start,
+                          float* obs_mask, float* latent_mask, float* mask, int64_t* frame_indices, int W, int K, int V, int Tv,
+                          int frame_elems, void* stream);
+int lfvdm_search_noise_qsample(const float* x_start, const int32_t* table, const int64_t* t_list, int32_t* ctl,
+                               const int64_t* key, const float* sqrt_acp, const float* sqrt_1macp, float* noise, float* x_t,
+                               int64_t* t_buf, int W, int K, int V, int frame_elems, void* stream);
+int lfvdm_search_noise_fill(const int32_t* table, uint64_t seed, int step, int j, float* noise, int W, int K, int V,
+                            int frame_elems, void* stream);
+int lfvdm_search_scores(const float* terms, const int64_t* t_list, float* scores, int G, int V, int n_t, int ld, int col_base,
+                        void* stream);
+
 /* Input compositing of the TRAINING forward (unet.py:441-450) as channels-last rows [N*H*W][ld] for the first 3x3 conv:
  * channels 0..Cx-1 = x*(1-obs[n]) + x0*obs[n], channel Cx = obs[n] (indicator), zero up to ld (>= Cx+1, multiple of 4).
  * x, x0: (N, Cx, H, W); obs: [N].  (Inference fuses this into lfvdm_conv_in; training keeps the rows for the weight

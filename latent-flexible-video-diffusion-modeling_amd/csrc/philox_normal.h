@@ -8,10 +8,12 @@
 //   NOISE_STREAM_UPDATE   0   the x_{t-1} update (lfvdm_update_rng_x0, lfvdm_conv_out_update_x0)
 //   NOISE_STREAM_BLEND    1   the known-region blend (lfvdm_known_blend)
 //   NOISE_STREAM_RENOISE  2   the re-noise step of resampling (lfvdm_renoise)
+//   NOISE_STREAM_SEARCH   3   the schedule search (schedule_search.hip: the low byte of the word, the window step above it;
+//                             its key is the search's seed and its other counter words are keyed by video frame, not by row)
 #pragma once
 #include "common_hip.h"
 
-enum { NOISE_STREAM_UPDATE = 0, NOISE_STREAM_BLEND = 1, NOISE_STREAM_RENOISE = 2 };
+enum { NOISE_STREAM_UPDATE = 0, NOISE_STREAM_BLEND = 1, NOISE_STREAM_RENOISE = 2, NOISE_STREAM_SEARCH = 3 };
 
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                               unsigned (&out)[4]) {

@@ -191,6 +191,10 @@ _SIGS = {
     "lfvdm_train_loss": ([c_fp] * 6 + [c_i] + [c_fp] * 3 + [c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_train_loss_bwd": ([c_fp] * 5 + [c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_prepare_batch": ([c_fp] * 6 + [c_i] * 4 + [c_fp], c_i),
+    "lfvdm_search_assemble": ([c_fp] * 9 + [c_i] * 5 + [c_fp], c_i),
+    "lfvdm_search_noise_qsample": ([c_fp] * 10 + [c_i] * 4 + [c_fp], c_i),
+    "lfvdm_search_noise_fill": ([c_fp, C.c_uint64, c_i, c_i, c_fp] + [c_i] * 4 + [c_fp], c_i),
+    "lfvdm_search_scores": ([c_fp, c_fp, c_fp] + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_chain_plan": ([C.POINTER(ChainStage), c_i, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], c_i),
     "lfvdm_chain_conv_ok": ([C.POINTER(ConvArgs)], c_i),
@@ -842,3 +846,41 @@ def jobs_to_device(jobs, device):
     arr = (type(jobs[0]) * len(jobs))(*jobs)
     raw = bytes(memoryview(arr))
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+
+
+SLOT_PAD, SLOT_OBS, SLOT_LATENT = 0, 1, 2      # LFVDM_SLOT_* of include/lfvdm_hip.h
+
+
+def search_assemble(pool, table, role, x0, x_start, obs_mask, latent_mask, mask, frame_indices):
+    """Windows of the schedule search (lfvdm_search_assemble): pool (V, Tv, ...) fp32, table / role (W, K) int32 -> x0 /
+    x_start (W, K, ...), obs_mask / latent_mask / mask (W * K floats each), frame_indices (W, K) int64."""
+    V, Tv = pool.shape[:2]
+    W, K = table.shape
+    check(lib().lfvdm_search_assemble(ptr(pool), ptr(table, torch.int32), ptr(role, torch.int32), ptr(x0), ptr(x_start),
+                                      ptr(obs_mask), ptr(latent_mask), ptr(mask), ptr(frame_indices, torch.int64), W, K, V, Tv,
+                                      pool[0, 0].numel(), stream()), "lfvdm_search_assemble")
+
+
+def search_noise_qsample(x_start, table, t_list, ctl, key, sa, sb, noise, x_t, t_buf, V):
+    """Head of the search's replayed step (lfvdm_search_noise_qsample): position ctl[0] of ``t_list`` (ctl: int32 [4] =
+    position, ticket, list length, unused; key: int64 [2] = seed, window step) -> t_buf, noise, x_t; ctl[0] += 1."""
+    W, K = table.shape
+    check(lib().lfvdm_search_noise_qsample(ptr(x_start), ptr(table, torch.int32), ptr(t_list, torch.int64), ptr(ctl, torch.int32),
+                                           ptr(key, torch.int64), ptr(sa), ptr(sb), ptr(noise), ptr(x_t), ptr(t_buf, torch.int64),
+                                           W, K, int(V), x_start[0, 0].numel(), stream()), "lfvdm_search_noise_qsample")
+
+
+def search_noise_fill(table, seed, step, j, noise, V):
+    """The search's noise of timestep position ``j`` for the windows of ``table`` (lfvdm_search_noise_fill) -> ``noise``
+    (W, K, ...)."""
+    W, K = table.shape
+    check(lib().lfvdm_search_noise_fill(ptr(table, torch.int32), int(seed) & (2 ** 64 - 1), int(step), int(j), ptr(noise), W, K,
+                                        int(V), noise[0, 0].numel(), stream()), "lfvdm_search_noise_fill")
+
+
+def search_scores(terms, t_list, scores, G, V, col_base=-1):
+    """scores[g] = mean over the V windows of candidate g and the positions of ``t_list`` of ``terms`` (W, ld)
+    (lfvdm_search_scores); ``col_base`` as in ``vb_terms``."""
+    n_t = t_list.numel() if t_list is not None else terms.shape[1]
+    check(lib().lfvdm_search_scores(ptr(terms), ptr(t_list, torch.int64) if t_list is not None else None, ptr(scores), int(G),
+                                    int(V), n_t, terms.shape[1], int(col_base), stream()), "lfvdm_search_scores")

@@ -12,7 +12,9 @@ class ReplayedStep:
     table build, the warm-up and capture of ``_step_body`` (the subclass's), the chain-timeout check and the fall-back,
     and ``step``: a single replay."""
 
-    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise):
+    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise, time_tables=True):
+        # time_tables=False: a plan WITHOUT timestep tables (the embedding and RPE launches stay in the step) - for a step whose
+        # frame indices change from one replay to the next, where a table keyed by this chain's frames would be rebuilt every time
         # inject_noise (parity tests): the replayed step READS ``self.noise`` - the caller fills it before every
         # ``step`` - instead of drawing it (the reference's th.randn_like, gaussian_diffusion.py:396)
         self.diffusion, self.unet, self.shape = diffusion, unet, tuple(shape)
@@ -29,7 +31,7 @@ class ReplayedStep:
         self.engine = unet.native_engine()
         # the chain walks a known schedule: everything that depends on (t, frame_indices) alone is tabulated once per
         # chain (Plan.build_time_tables / build_R_tables) instead of being recomputed by four launches in every step
-        self.plan = Plan(self.engine, B, T, H, W, False, time_steps=diffusion.num_timesteps)
+        self.plan = Plan(self.engine, B, T, H, W, False, time_steps=diffusion.num_timesteps if time_tables else None)
         self.plan.refresh_weights()
         dev = self.plan.dev
         self.tb = diffusion.tables(dev)
