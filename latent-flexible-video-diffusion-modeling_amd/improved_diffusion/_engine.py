@@ -22,7 +22,8 @@ import weakref
 import torch as th
 import torch.nn as nn
 
-from . import _native as nat
+from . import _chains, _native as nat
+from ._chains import CHAIN_MAX_M, CHAIN_TIMEOUT_S, chain_local_enabled, level_chain_enabled  # noqa: F401 (re-exported)
 from .nn import timestep_freqs
 
 
@@ -61,28 +62,7 @@ TEMPORAL_QKV = os.environ.get("LFVDM_TEMPORAL_QKV", "1") != "0"
 GN_EPILOGUE = os.environ.get("LFVDM_GN_EPILOGUE", "1") != "0"
 # LFVDM_NEXT_GN_EPILOGUE=0: never evaluate the NEXT ResBlock's first GroupNorm in a producer's epilogue (A/B aid)
 NEXT_GN_EPILOGUE = os.environ.get("LFVDM_NEXT_GN_EPILOGUE", "1") != "0"
-# LFVDM_LEVEL_CHAIN=0: every launch of the low-resolution levels stays its own launch (A/B aid; the persistent level chain
-# is bitwise the per-launch plan with the same tile codes).  LFVDM_CHAIN_MAX_M: launches with at most this many output rows
-# (N * Ho * Wo) are candidates (640 = the 4x4 and 2x2 levels of the 20-frame, batch-2 headline configuration)
-def level_chain_enabled():
-    """Read when a plan is built / tuned (not at import): a process that learns late that it SHARES its GPU with another
-    process - bench.py's N-ranks-on-fewer-cards rehearsal - switches the chains off for the plans it builds afterwards.  A
-    chain needs all its workgroups co-resident; two processes' chains on one card can each get part of the CUs and wait for
-    workgroups that cannot start (every wait is bounded: the timeout raises the abort word and the sampler falls back, but
-    that costs LFVDM_CHAIN_TIMEOUT_S seconds)."""
-    return os.environ.get("LFVDM_LEVEL_CHAIN", "1") != "0"
-
-
-def chain_local_enabled():
-    """LFVDM_CHAIN_LOCAL=0: the chains keep the split-K tile body of round 5 for every stage (A/B aid).  Default: stages on
-    maps of <= 16 pixels run SAMPLE-LOCAL (csrc/conv_local_body.h: whole samples x 16 filters x all of K per work item, filter
-    slice resident in LDS before the item's flags arrive, no split-K seam, GroupNorm inside one wave)."""
-    return os.environ.get("LFVDM_CHAIN_LOCAL", "1") != "0"
-
-
-CHAIN_MAX_M = int(os.environ.get("LFVDM_CHAIN_MAX_M", "640"))
 MAX_FRAMES = 64       # frames per window of the temporal attention kernels (lfvdm_attn_temporal*)
-CHAIN_TIMEOUT_S = float(os.environ.get("LFVDM_CHAIN_TIMEOUT_S", "2.0"))
 
 
 class _TableBudget:
@@ -141,7 +121,10 @@ class Plan:
         self.steps = []     # (callable, args) executed in order; every callable takes the stream last
         self.packs = []     # (conv weight parameter, packed buffer)
         self.attn_t, self.attn_s = [], []
-        self.chains = []    # persistent level chains (build_chains): dicts with the device tables and the steps they replace
+        self.chains = []    # persistent level chains (_chains.make_chain): dicts with the device tables and the steps they replace
+        self.chains_off = False     # chains were taken apart (disable_chains / split_chains): build_chains builds none again
+        self.skip_side = []         # (step, the tensor it waits for): the skip side of the decoder's split concat convolutions
+        self.part_bases = {}        # output pointer of a lfvdm_gn_apply_part launch -> (base, first column) of the concat operand
         self._build()
 
     # ------------------------------------------------------------------ helpers
@@ -541,11 +524,9 @@ class Plan:
             a = self.conv_args(gn=gn, gn_out=actL, gn_act=nat.ACT_SILU, gn_skip_raw=0, gn_gw=gw, gn_ld=C0, **kw)
             nt, nw = C.c_int(), C.c_int()
             if GN_EPILOGUE and L.lfvdm_conv_igemm_config(C.byref(a), C.byref(nt), C.byref(nw)) == 0:
-                self.part_bases = getattr(self, "part_bases", {})
                 self.part_bases[_p(actR)] = (_p(actR), 0)
                 self.add(L.lfvdm_gn_apply_part, _p(sb), C1, N, P, gw, _p(gn.weight) + 4 * C0, _p(gn.bias) + 4 * C0, gn.eps,
                          nat.ACT_SILU, _p(actR), C1)
-                self.skip_side = getattr(self, "skip_side", [])
                 self.skip_side.append((self.steps[-1], _p(sb)))         # (step, the tensor it waits for)
                 self.add_conv_args(a)
                 self._cat_done = (actL, actR)
@@ -556,7 +537,6 @@ class Plan:
         if not GN_EPILOGUE or L.lfvdm_conv_igemm_config(C.byref(a), C.byref(nt), C.byref(nw)) != 0:
             return False
         out_ptr = _p(act) + 4 * C0
-        self.part_bases = getattr(self, "part_bases", {})
         self.part_bases[out_ptr] = (_p(act), C0)
         self.add(L.lfvdm_gn_apply_part, _p(sb), C1, N, P, gw, _p(gn.weight) + 4 * C0, _p(gn.bias) + 4 * C0, gn.eps, nat.ACT_SILU,
                  out_ptr, Ccat)
@@ -873,8 +853,7 @@ class Plan:
                 continue
             a = args[0]._obj
             key = nat.tune_key(a)
-            if (level_chain_enabled() and a.N * a.Ho * a.Wo <= CHAIN_MAX_M and a.out_mode == nat.OUT_ROWS
-                    and self._local_tiles(a) == 0):
+            if _chains.tile_stage_candidate(a):
                 # candidate stage of a persistent level chain: the fastest code among the variants the chain kernel holds
                 # (own cache entry: the unrestricted choice of the same shape stays what the other callers get)
                 ckey = key + (nat.TUNE_CHAIN,)
@@ -906,344 +885,9 @@ class Plan:
             self.tune_chains()
         return tuned
 
-    # ------------------------------------------------------------------ persistent level chains
-    def _local_tiles(self, a):
-        """Row tiles per work item (1 | 2) if this launch runs as a SAMPLE-LOCAL chain stage, else 0.  One tile of 16 rows
-        per item while the stage then fits one round of 256 workgroups, else two."""
-        L = nat.lib()
-        if not (chain_local_enabled() and level_chain_enabled()) or a.N * a.Ho * a.Wo > CHAIN_MAX_M or a.out_mode != nat.OUT_ROWS:
-            return 0
-        forced = int(os.environ.get("LFVDM_CHAIN_LOCAL_RT", "0")) or int(nat.tune_cache().get(nat.tune_key(a) + (nat.TUNE_LOCAL_RT,), 0))
-        M, NS = a.N * a.Ho * a.Wo, a.Cout // 16
-        order = (1, 2) if -(-M // 16) * NS <= 256 else (2, 1)
-        for rt in ((forced,) if forced else order):
-            if L.lfvdm_chain_local_ok(C.byref(a), rt) == 0:
-                return rt
-        return 0
-
-    def _chain_stage(self, step):
-        """-> ChainStage for a step that can run inside a persistent level chain, else None."""
-        L = nat.lib()
-        fn, args = step
-        st = nat.ChainStage()
-        if fn is L.lfvdm_conv_igemm:
-            a = args[0]._obj
-            rt = self._local_tiles(a)
-            if rt:
-                st.kind, st.cfg = nat.CHAIN_LOCAL, rt
-                C.memmove(C.byref(st.conv), C.byref(a), C.sizeof(nat.ConvArgs))
-                return st
-            if a.N * a.Ho * a.Wo > CHAIN_MAX_M or L.lfvdm_chain_conv_ok(C.byref(a)) != 0:
-                return None
-            st.kind = nat.CHAIN_CONV
-            C.memmove(C.byref(st.conv), C.byref(a), C.sizeof(nat.ConvArgs))
-            return st
-        if fn is L.lfvdm_gn_apply_part:
-            (src, Cp, N, P, cg, gamma, beta, eps, act, out, ldo) = args
-            if N * P > CHAIN_MAX_M or L.lfvdm_chain_gn_ok(Cp, 0, N, P) != 0:
-                return None
-            st.kind = nat.CHAIN_GN
-            g = st.gn
-            g.src0, g.src1, g.C0, g.C1, g.N, g.P = src, None, Cp, 0, N, P
-            g.gamma, g.beta, g.film, g.film_div, g.film_ld, g.eps, g.act, g.out = gamma, beta, None, 1, 0, eps, act, out
-            g.cg, g.ldo = cg, ldo
-            g.out_base, g.out_col = self.part_bases[out]
-            return st
-        if fn is L.lfvdm_gn_apply:
-            (src0, src1, C0, C1, N, P, gamma, beta, film, film_div, film_ld, eps, act, out, cA, cB, stats) = args
-            if N * P > CHAIN_MAX_M or cA or cB or stats or L.lfvdm_chain_gn_ok(C0, C1, N, P) != 0:
-                return None
-            st.kind = nat.CHAIN_GN
-            g = st.gn
-            g.src0, g.src1, g.C0, g.C1, g.N, g.P = src0, src1, C0, C1, N, P
-            g.gamma, g.beta, g.film, g.film_div, g.film_ld, g.eps, g.act, g.out = gamma, beta, film, film_div, film_ld, eps, act, out
-            return st
-        return None
-
-    def _make_chain(self, run, keep=True):
-        """One lfvdm_level_chain step for a run of chainable steps (list of (step, ChainStage)), or None.  keep=False: the
-        device tables live only as long as the returned dict (the in-chain tuner builds hundreds of candidates)."""
-        L = nat.lib()
-        n = len(run)
-        # stages that read nothing the chain produces (the skip half of a concat GroupNorm) first: the planner puts them on
-        # idle workgroups, and a workgroup walks the stages in list order - at the front they run at once
-        def outs_of(st):
-            return ({st.conv.out, st.conv.gn_out} if st.kind != nat.CHAIN_GN else {st.gn.out_base or st.gn.out}) - {None}
-
-        def srcs_of(st):
-            if st.kind == nat.CHAIN_GN:
-                return {st.gn.src0, st.gn.src1} - {None}
-            cv = st.conv
-            return {cv.src0, cv.src1, cv.s2src0, cv.s2src1, cv.res} - {None}
-
-        # free-standing stages: GroupNorms of tensors from earlier launches (the skip half of a concat normalisation) and
-        # sample-local convolutions that read nothing else (the skip half of a split concat convolution)
-        produced = set()
-        for _, st in run:
-            produced |= outs_of(st)
-        free_gn = [st for _, st in run if st.kind == nat.CHAIN_GN and not (srcs_of(st) & produced)]
-        gn_outs = set()
-        for st in free_gn:
-            gn_outs |= outs_of(st)
-        free_ids = {id(st) for st in free_gn}
-        free_ids |= {id(st) for _, st in run if st.kind == nat.CHAIN_LOCAL and srcs_of(st) and srcs_of(st) <= gn_outs}
-        free_ids |= {id(st) for _, st in run if st.side}
-        run = [e for e in run if id(e[1]) in free_ids] + [e for e in run if id(e[1]) not in free_ids]
-        stages = (nat.ChainStage * n)(*[st for _, st in run])
-        cap = 1 << 20
-        deps = (C.c_int32 * cap)()
-        used, ws_f, cnt_i = C.c_int64(), C.c_int64(), C.c_int64()
-        n_flags, grid, lds = C.c_int32(), C.c_int32(), C.c_int32()
-        rc = L.lfvdm_chain_plan(stages, n, deps, cap, C.byref(used), C.byref(n_flags), C.byref(ws_f), C.byref(cnt_i),
-                                C.byref(grid), C.byref(lds))
-        if rc != 0:
-            return None
-        # the chain's waits only end if ALL its workgroups are resident: ask the device how many it holds with this much
-        # LDS (a partitioned / CU-masked / smaller part than the 256 CUs of a whole MI355X) and plan again under that cap
-        if self.dev.type == "cuda":
-            room = int(L.lfvdm_chain_capacity(lds.value))
-            if room < max(8, min(64, grid.value)):
-                _table_budget.log(f"persistent level chain refused: the device holds {room} of its workgroups at once")
-                return None
-            if grid.value > room:
-                grid = C.c_int32(room // 8 * 8)
-                rc = L.lfvdm_chain_plan(stages, n, deps, cap, C.byref(used), C.byref(n_flags), C.byref(ws_f), C.byref(cnt_i),
-                                        C.byref(grid), C.byref(lds))
-                if rc != 0 or grid.value > room:
-                    return None
-        ws = th.empty(max(1, ws_f.value), device=self.dev)
-        cnt = th.zeros(max(1, cnt_i.value), dtype=th.int32, device=self.dev)
-        for i in range(n):
-            if stages[i].kind != nat.CHAIN_GN:
-                cv = stages[i].conv
-                cv.splitk_ws, cv.splitk_cnt = _p(ws) + 4 * stages[i].ws_off, _p(cnt) + 4 * stages[i].cnt_off
-                cv.splitk_ws_floats, cv.splitk_cnt_ints = ws.numel() - stages[i].ws_off, cnt.numel() - stages[i].cnt_off
-        stages_dev = th.frombuffer(bytearray(bytes(memoryview(stages))), dtype=th.uint8).to(self.dev)
-        deps_dev = th.frombuffer(bytearray(bytes(memoryview(deps))[:4 * max(1, used.value)]), dtype=th.int32).to(self.dev)
-        flags = th.zeros(max(1, n_flags.value), dtype=th.int32, device=self.dev)
-        ctl = th.zeros(nat.CHAIN_CTL_INTS, dtype=th.int32, device=self.dev)
-        ch = dict(steps=[st for st, _ in self._launch_order(run)], run=list(run), n=n, ctl=ctl, grid=grid.value, lds=lds.value,
-                  items=[s.n_items for s in stages], kinds=[s.kind for s in stages], codes=[s.conv.tune for s in stages],
-                  room=(room if self.dev.type == "cuda" else None),
-                  tensors=[ws, cnt, stages_dev, deps_dev, flags, ctl])
-        ch["step"] = (L.lfvdm_level_chain, (_p(stages_dev), n, _p(deps_dev), _p(flags), _p(ctl), grid.value, lds.value,
-                                            CHAIN_TIMEOUT_S))
-        if keep:
-            self.keep += ch["tensors"]
-        return ch
-
-    def _launch_order(self, run):
-        """The run in the order of the plan's step list (what ``disable_chains`` restores): hoisted stages go back to where
-        their launches stood."""
-        pos = self._step_pos          # (positions in the per-launch step list, recorded by build_chains)
-        return sorted(run, key=lambda e: pos[id(e[0])])
-
-    def _time_chain(self, ch, reps, rounds):
-        """Microseconds per launch of one chain on its own, back to back (minimum over `rounds`)."""
-        fn, args = ch["step"]
-        s = nat.stream()
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        for _ in range(3):
-            fn(*args, s)
-        best = float("inf")
-        for _ in range(rounds):
-            e0.record()
-            for _ in range(reps):
-                fn(*args, s)
-            e1.record()
-            e1.synchronize()
-            best = min(best, 1000.0 * e0.elapsed_time(e1) / reps)
-        if int(ch["ctl"][nat.CHAIN_CTL_ABORT].item()) != 0:
-            return float("inf")
-        return best
-
-    def tune_chains(self, reps=20, rounds=3):
-        """Tile codes of the chains' GEMM stages chosen INSIDE the chain (one pass of coordinate descent: every legal code
-        of a stage with the other stages at their current choice, the chain timed on its own).  A stand-alone launch and a
-        chain stage have different optima: in a chain the filter pieces are in flight before the wait, so a third LDS-DMA
-        stage (the whole K slice of a k-group requested up front) pays where it did not per launch, and a stage with more
-        work items than workgroups runs in rounds.  Cached per launch shape (key + TUNE_IN_CHAIN)."""
-        if not self.chains or th.cuda.is_current_stream_capturing():
-            return 0
-        L, cache, changed = nat.lib(), nat.tune_cache(), 0
-        reps = int(os.environ.get("LFVDM_TUNE_REPS", reps))
-        rounds = int(os.environ.get("LFVDM_TUNE_ROUNDS", rounds))
-        codes = (C.c_int * 256)()
-        for ci in range(len(self.chains)):
-            ch = self.chains[ci]
-            run, cur, cur_t = ch["run"], ch, None
-            for si, (step, st) in enumerate(run):
-                if st.kind == nat.CHAIN_LOCAL:
-                    # row tiles per item (1 | 2) of a sample-local stage, measured in the chain: one tile = more items (a second
-                    # round where they outnumber the workgroups), two = half the filter fetches per output row
-                    a = step[1][0]._obj
-                    key = nat.tune_key(a) + (nat.TUNE_LOCAL_RT,)
-                    if os.environ.get("LFVDM_CHAIN_LOCAL_RT"):
-                        continue
-                    if key in cache:                   # (measured on an earlier stage of the same shape, or in another plan)
-                        if cache[key] != st.cfg and L.lfvdm_chain_local_ok(C.byref(st.conv), cache[key]) == 0:
-                            old_rt, st.cfg = st.cfg, cache[key]
-                            nxt = self._make_chain(run, keep=False)
-                            if nxt is not None:
-                                cur, cur_t = nxt, None
-                            else:
-                                st.cfg = old_rt
-                        continue
-                    other = 3 - st.cfg
-                    best_rt = st.cfg
-                    if L.lfvdm_chain_local_ok(C.byref(st.conv), other) == 0:
-                        if cur_t is None:
-                            cur_t = self._time_chain(cur, reps, rounds)
-                        st.cfg = other
-                        cand = self._make_chain(run, keep=False)
-                        t = self._time_chain(cand, reps, rounds) if cand is not None else float("inf")
-                        if t < cur_t * 0.995:
-                            cur, cur_t, best_rt = cand, t, other
-                        st.cfg = best_rt
-                    cache[key] = best_rt
-                    continue
-                if st.kind != nat.CHAIN_CONV:
-                    continue
-                a = step[1][0]._obj
-                key = nat.tune_key(a) + (nat.TUNE_IN_CHAIN,)
-                if key in cache:
-                    if cache[key] != st.conv.tune:
-                        old_code = st.conv.tune
-                        st.conv.tune = a.tune = cache[key]
-                        nxt = self._make_chain(run, keep=False)
-                        if nxt is not None:
-                            cur, cur_t = nxt, None
-                        else:       # the cached code does not plan in THIS chain: the stage keeps the code it runs with
-                            st.conv.tune = a.tune = old_code
-                    continue
-                if cur_t is None:
-                    cur_t = self._time_chain(cur, reps, rounds)
-                n = L.lfvdm_conv_igemm_candidates(C.byref(a), codes, 256)
-                start = st.conv.tune
-                best_code = start
-                for code in [codes[i] for i in range(n)]:
-                    if code == start:
-                        continue
-                    st.conv.tune = code
-                    if L.lfvdm_chain_conv_ok(C.byref(st.conv)) != 0:
-                        continue
-                    cand = self._make_chain(run, keep=False)
-                    if cand is None:
-                        continue
-                    t = self._time_chain(cand, reps, rounds)
-                    if t < cur_t * 0.995:
-                        cur, cur_t, best_code = cand, t, code
-                st.conv.tune = a.tune = best_code
-                cache[key] = best_code
-            if cur is not ch:
-                changed += 1
-                self.keep += cur["tensors"]
-                idx = next(i for i, stp in enumerate(self.steps) if stp is ch["step"])
-                self.steps[idx] = cur["step"]
-                self.chains[ci] = cur
-        nat.tune_cache_save()
-        return changed
-
-    def build_chains(self):
-        """Replace every run of >= 2 consecutive chainable launches (tuned implicit GEMMs and one-wave GroupNorms of the
-        low-resolution levels) by ONE persistent launch (lfvdm_level_chain).  Idempotent; called by ``autotune``."""
-        if not level_chain_enabled() or self.chains or getattr(self, "chains_off", False):
-            return 0
-        head_last = self.head["step"] == len(self.steps) - 1
-        self._step_pos = {id(sp): i for i, sp in enumerate(self.steps)}
-        # runs of consecutive chainable steps
-        runs, lone = [], []           # runs: [(first position, [(step, stage)...])]; lone: (position, step)
-        run = []
-        for i, step in enumerate(self.steps):
-            st = self._chain_stage(step)
-            if st is not None:
-                run.append((step, st))
-            else:
-                if run:
-                    runs.append((self._step_pos[id(run[0][0])], run))
-                    run = []
-                lone.append((i, step))
-        if run:
-            runs.append((self._step_pos[id(run[0][0])], run))
-        # The SKIP SIDE of the decoder's split concat convolutions (GroupNorm of the encoder's skip tensor, then the skip half
-        # of the convolution: _final_conv_cat / _res) depends on nothing the decoder computes: SIDE stages of their chain
-        # (lfvdm_chain_stage.side: the planner reserves part of the grid for them), listed first and in the order in which the
-        # main path needs them, they run beside it from the first microsecond - their operands come from earlier launches.
-        # Measured alternatives: on shared workgroups at the front of the chain they kept the main path's first workgroups
-        # busy for ~20 us; moved into the encoder-side chain (tail, shared workgroups) they started when that chain's main
-        # path had ended (+34 us), and on a reserved quarter of that chain's grid they took 100 us for its 64.
-        if os.environ.get("LFVDM_SKIP_SIDE", "1") != "0":
-            for step, _ in getattr(self, "skip_side", []):
-                for _, r in runs:
-                    for sp, st in r:
-                        if sp is step and any(not x.side and x is not st for _, x in r):
-                            st.side = 1
-        out = []
-        for pos, step in sorted([(p, ("run", r)) for p, r in runs if r] + [(p, ("step", sp)) for p, sp in lone], key=lambda e: e[0]):
-            if step[0] == "step":
-                out.append(step[1])
-                continue
-            r = step[1]
-            # (LFVDM_CHAIN_SINGLE=1: a lone sample-local launch - the 1x1 projections between the attention kernels of the middle
-            # block - as a one-stage "chain".  Measured and left off: 7.7 us per launch against 5.6 for the tile kernel on
-            # those 160-row, K = 128 GEMMs - with nothing to wait for, the filter fetch in front of the K loop is exposed)
-            single = len(r) == 1 and r[0][1].kind == nat.CHAIN_LOCAL and os.environ.get("LFVDM_CHAIN_SINGLE", "0") == "1"
-            ch = self._make_chain(r) if len(r) >= 2 or single else None
-            if ch is None:
-                out.extend(sp for sp, _ in r)
-            else:
-                self.chains.append(ch)
-                out.append(ch["step"])
-        self.steps = out
-        if head_last:
-            self.head["step"] = len(self.steps) - 1
-        return len(self.chains)
-
-    def disable_chains(self):
-        """Back to one launch per stage (after a chain reported a timeout, or for A/B runs)."""
-        if not self.chains:
-            self.chains_off = True
-            return
-        head_last = self.head["step"] == len(self.steps) - 1
-        by_step = {id(ch["step"]): ch for ch in self.chains}
-        out = []
-        for step in self.steps:
-            ch = by_step.get(id(step))
-            out.extend(ch["steps"] if ch is not None else [step])
-        self.steps, self.chains, self.chains_off = out, [], True
-        if head_last:
-            self.head["step"] = len(self.steps) - 1
-
-    def split_chains(self):
-        """Every stage of every chain as a chain of its own (one launch per stage, the SAME kernel bodies and work items: no
-        flag is waited for, the launch boundary orders the stages).  Bitwise the chained plan - the guard that a hand-off
-        inside a chain never delivers a stale byte; also what a plan falls back to where it must not depend on co-residency
-        but wants the same numerics."""
-        if not self.chains:
-            return 0
-        head_last = self.head["step"] == len(self.steps) - 1
-        by_step = {id(ch["step"]): ch for ch in self.chains}
-        out, n = [], 0
-        for step in self.steps:
-            ch = by_step.get(id(step))
-            if ch is None:
-                out.append(step)
-                continue
-            for sp, st in self._launch_order(ch["run"]):
-                one = self._make_chain([(sp, st)])
-                assert one is not None
-                out.append(one["step"])
-                n += 1
-        self.steps, self.chains, self.chains_off = out, [], True
-        if head_last:
-            self.head["step"] = len(self.steps) - 1
-        return n
-
-    def chains_aborted(self):
-        """Did a wait inside a persistent level chain time out?  (synchronises: ONE read-back for all chains)"""
-        if not self.chains:
-            return False
-        return bool(th.stack([ch["ctl"][nat.CHAIN_CTL_ABORT] for ch in self.chains]).ne(0).any().item())
+    # ------------------------------------------------------------------ persistent level chains: _chains.py
+    build_chains, tune_chains = _chains.build, _chains.tune
+    disable_chains, split_chains, chains_aborted = _chains.disable, _chains.split, _chains.aborted
 
     # ------------------------------------------------------------------ run
     def weight_signature(self):

@@ -331,14 +331,29 @@ def test_cfgB_plan_becomes_two_sample_local_chains_with_a_skip_side():
     import bench
     from improved_diffusion import _engine as eng
     model, _ = bench.make_model_and_diffusion(64, th.device("cpu"))
-    pl = eng.Plan(eng.Engine(model), 2, 20, 16, 16, False, time_steps=1000)
     L = nat.lib()
+
+    def fresh_plan():
+        pl = eng.Plan(eng.Engine(model), 2, 20, 16, 16, False, time_steps=1000)
+        # the chain state exists from construction on, and the launch order of a chain's stages is no hidden attribute
+        assert pl.chains == [] and pl.chains_off is False and not hasattr(pl, "_step_pos")
+        # four split concat convolutions; each lists two launches: the skip tensor's GroupNorm and the skip half of the conv
+        assert isinstance(pl.skip_side, list) and len(pl.skip_side) == 2 * 4
+        assert [step[0] for step, _ in pl.skip_side] == [L.lfvdm_gn_apply_part, L.lfvdm_conv_igemm] * 4
+        for fn, args in pl.steps:                  # (stand-in for the autotuner: a chain-legal tile code for the tile stages)
+            if fn is L.lfvdm_conv_igemm and args[0]._obj.N * args[0]._obj.Ho * args[0]._obj.Wo <= 640:
+                args[0]._obj.tune = code(6, 4, 2)
+        return pl
+
+    pl = fresh_plan()
     n_launches = len(pl.steps)
-    for fn, args in pl.steps:                      # (stand-in for the autotuner: a chain-legal tile code for the tile stages)
-        if fn is L.lfvdm_conv_igemm and args[0]._obj.N * args[0]._obj.Ho * args[0]._obj.Wo <= 640:
-            args[0]._obj.tune = code(6, 4, 2)
+    per_launch = [id(s) for s in pl.steps]
     assert pl.build_chains() == 2 and len(pl.steps) == n_launches - 28 + 2
     enc, dec = pl.chains
+    for ch in pl.chains:            # a chain stands for a contiguous slice of the per-launch step list, in that order
+        first = per_launch.index(id(ch["steps"][0]))
+        assert [id(s) for s in ch["steps"]] == per_launch[first:first + ch["n"]]
+        assert any(s is ch["step"] for s in pl.steps)
     assert enc["kinds"] == [nat.CHAIN_LOCAL] * 8 and enc["grid"] == 256
     assert dec["n"] == 20 and dec["kinds"][:8] == [nat.CHAIN_GN, nat.CHAIN_LOCAL] * 4 and set(dec["kinds"][8:]) == {nat.CHAIN_LOCAL}
     side = [st.side for _, st in dec["run"]]
@@ -354,3 +369,16 @@ def test_cfgB_plan_becomes_two_sample_local_chains_with_a_skip_side():
     order = [id(s) for s in pl.steps]
     for step, waits_for in pl.skip_side:                             # producer before consumer in the per-launch order
         assert id(step) in order
+    assert order == per_launch and pl.chains_off is True             # the same step objects in the same order
+    assert pl.build_chains() == 0 and [id(s) for s in pl.steps] == per_launch and not pl.chains
+    # every stage as a chain of its own: 8 + 20 one-stage launches of the chain kernel (planned and allocated, not launched)
+    pl2 = fresh_plan()
+    assert pl2.build_chains() == 2
+    chain_steps = {id(ch["step"]) for ch in pl2.chains}
+    was_chain = [id(s) in chain_steps for s in pl2.steps]
+    assert pl2.split_chains() == 28 and pl2.chains == [] and len(pl2.steps) == n_launches
+    singles = [s for s in pl2.steps if s[0] is L.lfvdm_level_chain]
+    assert len(singles) == 28 and all(args[1] == 1 for _, args in singles)
+    # ... standing where their chains stood
+    i = was_chain.index(True)
+    assert all(s[0] is L.lfvdm_level_chain for s in pl2.steps[i:i + 8])
