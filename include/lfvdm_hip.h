@@ -703,6 +703,28 @@ int lfvdm_vb_terms_bwd(const float* x_start, const float* x_t, const float* mode
                        const float* model_log_var, const float* mask, const float* g, int mean_type, int clip, float* d_out,
                        int B, int T, int frame_inner, void* stream);
 
+/* Video prediction metrics: per frame, the mean squared error and the mean SSIM (Wang et al. 2004) of K predicted samples
+ * against one ground truth, one pass over the pixels in their (B, T, C, H, W) layout.
+ *   pred  [K][N][C][H][W], truth [N][C][H][W] (N = videos x frames; truth is shared by the K samples through its index,
+ *   never replicated), both of `dtype` LFVDM_PIX_F32 (float) or LFVDM_PIX_U8 (uint8_t); value = scale * raw + shift maps
+ *   the data into [0, 1] (float data in [-1, 1]: 0.5, 0.5; uint8: 1 / 255, 0).
+ *   mse[k][n]  = mean over all C * H * W pixels of the squared difference of the [0, 1] values (PSNR = -10 log10 mse is the
+ *                caller's; the kernel never forms an inf)
+ *   ssim[k][n] = mean over the C channels and the (H - 10) * (W - 10) valid positions of
+ *                (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_x^2 + s_y^2 + C2)), C1 = 0.01^2, C2 = 0.03^2,
+ *                all five moments from one separable 11 x 11 Gaussian window (sigma 1.5, sum 1), biased, no padding.
+ * partials: scratch of at least the floats the _workspace entry returns for the same shape (two per workgroup; every
+ * slot is written before it is read, nothing needs clearing).  Two kernels, no float atomics: bitwise reproducible, and
+ * the same bits for every k that holds the same sample.  16-byte loads where pred, truth and the row pitch allow (W a
+ * multiple of 4 floats / 16 bytes), scalar loads otherwise.  H < 11 or W < 11, a non-positive dimension, an unknown dtype, a
+ * NULL pointer or partials_floats below the workspace size -> LFVDM_E_SHAPE, before anything is launched. */
+#define LFVDM_PIX_F32 0
+#define LFVDM_PIX_U8 1
+int lfvdm_frame_metrics(const void* pred, const void* truth, int dtype, float scale, float shift, int K, int N, int C, int H,
+                        int W, float* mse, float* ssim, float* partials, long partials_floats, void* stream);
+/* floats of `partials` the launch above needs; 0 for a shape it refuses */
+long lfvdm_frame_metrics_workspace(int K, int N, int C, int H, int W);
+
 /* ---------------------------------------------------------------------------------------
  * Fused AdamW + EMA + gradient-norm over one flat fp32 arena (train_util.py:346-357, nn.py:55-65).
  * torch.optim.AdamW semantics (decoupled weight decay, bias correction); ema <- rate*ema + (1-rate)*p.

@@ -140,6 +140,8 @@ _SIGS = {
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_vb_terms": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 4 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_vb_terms_bwd": ([c_fp] * 11 + [c_i, c_i, c_fp, c_i, c_i, c_i, c_fp], c_i),
+    "lfvdm_frame_metrics": ([c_fp, c_fp, c_i, C.c_float, C.c_float] + [c_i] * 5 + [c_fp, c_fp, c_fp, C.c_long, c_fp], c_i),
+    "lfvdm_frame_metrics_workspace": ([c_i] * 5, C.c_long),
     "lfvdm_gn_bwd_stats": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp], c_i),
     "lfvdm_gn_bwd_apply": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_bwd_apply_params": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i,
@@ -760,6 +762,27 @@ def vb_terms_bwd(x_start, x_t, out, t, recip, recipm1, c1, c2, model_logvar, mas
     check(lib().lfvdm_vb_terms_bwd(ptr(x_start), ptr(x_t), ptr(out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), ptr(c1), ptr(c2),
                                    ptr(model_logvar), ptr(mask), ptr(g), int(mean_type), int(bool(clip)), ptr(d_out), B, T,
                                    x_t.numel() // (B * T), stream()), "lfvdm_vb_terms_bwd")
+
+
+PIX_F32, PIX_U8 = 0, 1
+_PIX = {torch.float32: PIX_F32, torch.uint8: PIX_U8}
+
+
+def frame_metrics_workspace(K, N, C, H, W):
+    """Floats of scratch ``frame_metrics`` needs for this shape (lfvdm_frame_metrics_workspace); 0: the shape is refused."""
+    return int(lib().lfvdm_frame_metrics_workspace(K, N, C, H, W))
+
+
+def frame_metrics(pred, truth, scale, shift, K, N, C, H, W, mse, ssim, partials):
+    """Per-frame MSE and mean SSIM of ``pred`` (K, N, C, H, W) against ``truth`` (N, C, H, W), float32 or uint8, value =
+    scale * raw + shift in [0, 1]; ``mse`` / ``ssim``: (K, N) float32 (lfvdm_frame_metrics)."""
+    dt = pred.dtype
+    if dt not in _PIX or truth.dtype != dt:
+        raise RuntimeError(f"expected float32 or uint8 pixels of one dtype, got {pred.dtype} and {truth.dtype}")
+    if pred.numel() != K * N * C * H * W or truth.numel() != N * C * H * W or mse.numel() != K * N or ssim.numel() != K * N:
+        raise RuntimeError("frame_metrics: tensor sizes do not match (K, N, C, H, W)")
+    check(lib().lfvdm_frame_metrics(ptr(pred, dt), ptr(truth, dt), _PIX[dt], float(scale), float(shift), K, N, C, H, W, ptr(mse),
+                                    ptr(ssim), ptr(partials), partials.numel(), stream()), "lfvdm_frame_metrics")
 
 
 def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):
