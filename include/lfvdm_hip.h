@@ -370,7 +370,7 @@ int lfvdm_proj_gn(const float* o, const float* W, const float* bias, const float
 
 /* ---------------------------------------------------------------------------------------
  * Small-M grouped linear ("row-dot"): out[m][o] = sum_k actin(in[m][k]) * W[o][k] + b[o],
- * m < M <= 8.  One launch evaluates a whole table of jobs (time_embed.{0,2}, every
+ * m < M (eight batch rows share each pass over a weight row).  One launch evaluates a whole table of jobs (time_embed.{0,2}, every
  * ResBlock.emb_layers.1, every RPENet.embed_diffusion_time: nn.py:105-123, unet.py:303-308,
  * 157-163,196; rpe.py:29).  Job tables live in device memory (see lfvdm_rowdot_job).
  * in_mode: 0 = plain, 1 = SiLU(in), 2 = in is a scalar timestep per row and the operand is its

@@ -46,6 +46,22 @@ __device__ __forceinline__ float silu_f(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
 }
 
+// x * sigmoid(x) to (|x| + 4) * 2^-24 relative over the whole float range, for the embedding kernels (lfvdm_rowdot in_mode 1,
+// its backward, lfvdm_silu: a few thousand values per step - two more instructions and one more v_exp_f32 than silu_f, which
+// stays what the activation epilogues use).  silu_f misses that in two places:
+//  - __expf's single constant log2(e) is 1.3e-8 short, 0.22 |x| * 2^-24 in e^-x on top of the rounding of the product
+//    (1.16 times the bound at x = -44.68): here -x log2(e) is an fma over the constant split in two floats, rounded once;
+//  - below x = -87.34 the reciprocal of 1 + e^-x is a denormal, which v_rcp_f32 flushes to zero, and below -88.72 e^-x
+//    overflows: silu_f returns 0 where the value is still a normal float (-1.03e-36 at -87.34).  There 1 + e^-x is e^-x to
+//    float precision, so the value is x * e^x, evaluated as (x * 2^(64 - y)) * 2^-64 because v_exp_f32 flushes a denormal
+//    result as well (64 - y is exact for y in [64, 256]).
+__device__ __forceinline__ float silu_full_f(float v) {
+    const float y = __builtin_fmaf(v, -1.44269502f, v * -1.92596299e-8f);      // -v log2(e)
+    const float deep = (v * __builtin_amdgcn_exp2f(64.0f - y)) * 0x1p-64f;
+    const float shallow = v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y));
+    return v < -80.0f ? deep : shallow;
+}
+
 // floor(a / d) for 0 <= a < 2^21, d >= 1, rd = v_rcp_f32(d): the truncated product is off by at most one and the
 // fix-up repairs it (a generic 32-bit division is ~30 instructions; the normalisation kernels did eight per thread to
 // find the group of a channel)

@@ -813,7 +813,9 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const lfvdm_rowdot_job* __r
                     v.x = e[0]; v.y = e[1]; v.z = e[2]; v.w = e[3];
                 } else {
                     v = ld4(J.in + (size_t)(m0 + i) * J.ldin + k);
-                    if (J.in_mode == 1) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+                    if (J.in_mode == 1) {
+                        v.x = silu_full_f(v.x); v.y = silu_full_f(v.y); v.z = silu_full_f(v.z); v.w = silu_full_f(v.w);
+                    }
                 }
                 acc[i] += v.x * wv.x + v.y * wv.y + v.z * wv.z + v.w * wv.w;
             }
@@ -885,7 +887,9 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const lfvdm_rowdot_bwd_
                             }
                         } else {
                             f32x4 v = ld4(J.in + (size_t)(m0 + i) * J.ldin + k);
-                            if (J.in_mode == 1) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+                            if (J.in_mode == 1) {
+                                v.x = silu_full_f(v.x); v.y = silu_full_f(v.y); v.z = silu_full_f(v.z); v.w = silu_full_f(v.w);
+                            }
                             inv[i] = v;
                         }
                     }
@@ -1183,13 +1187,13 @@ namespace {
 __global__ __launch_bounds__(256) void silu_kernel(const float* __restrict__ in, float* __restrict__ out, long n4) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         f32x4 v = ld4(in + 4 * i);
-        v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w);
+        v.x = silu_full_f(v.x); v.y = silu_full_f(v.y); v.z = silu_full_f(v.z); v.w = silu_full_f(v.w);
         st4(out + 4 * i, v);
     }
 }
 }  // namespace
 
-// out = x * sigmoid(x), the very silu_f the row-dot launches apply to their inputs in in_mode 1: materialising it once
+// out = x * sigmoid(x), the very silu_full_f the row-dot launches apply to their inputs in in_mode 1: materialising it once
 // lets a launch with MANY batch rows (the sampler's per-chain tables) run in in_mode 0 instead of re-evaluating it per
 // output row.  n must be a multiple of 4.
 extern "C" int lfvdm_silu(const float* in, float* out, int64_t n, void* stream) {
