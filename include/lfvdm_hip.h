@@ -295,34 +295,45 @@ int lfvdm_gn_bwd_apply_params(const float* da, const float* src0, const float* s
                               float* out0, float* out1, int acc0, int acc1, const float* gamma, const float* beta,
                               const float* film, int film_ld, int T, float* dgamma, float* dbeta, float* dfilm,
                               int dfilm_ld, const float* add, int add_ld, void* stream);
-/* lfvdm_gn_bwd_stats + lfvdm_gn_bwd_apply_params in ONE launch (the training path): the per-channel sums stay in the
- * workgroup that owns the (sample, 8 groups) slice; dx is written (not accumulated) to out0 / out1.  add2 (optional, like
- * add): a third gradient of the same input - what the decoder's skip connection sends back to an encoder output. */
-int lfvdm_gn_bwd_fused(const float* da, const float* src0, const float* src1, int C0, int C1, int N, int P,
-                       const float* coefA, const float* coefB, const float* stats, int act, float* out0, float* out1,
-                       const float* gamma, const float* beta, const float* film, int film_ld, int T, float* dgamma,
-                       float* dbeta, float* dfilm, int dfilm_ld, const float* add, int add_ld, const float* add2,
-                       int add2_ld, void* stream);
-/* lfvdm_gn_bwd_fused for the deterministic mode: the same ONE launch (statistics + dx, add / add2 folded in), but the
- * per-(sample, channel) sums are STORED to sums[N][C][2] (each pair by exactly one workgroup) instead of being added to the
- * parameter gradients with float atomics; lfvdm_gn_param_grads then reduces them in sample order. */
-int lfvdm_gn_bwd_fused_sums(const float* da, const float* src0, const float* src1, int C0, int C1, int N, int P,
-                            const float* coefA, const float* coefB, const float* stats, int act, float* out0, float* out1,
-                            const float* add, int add_ld, const float* add2, int add2_ld, float* sums, void* stream);
-/* Large-map form of the GroupNorm backward (what lfvdm_gn_apply_ws is to the forward; reference nn.py:17-19 through
- * unet.py:194-207,399-403 at pixel-space map sizes): a workgroup owns a chunk of positions of a (sample, 8 groups) slice,
- * chunk sums -> fixed-order combination in every consumer workgroup -> dx: two launches of thousands of workgroups instead
- * of N*4 workgroups whatever P is.  ws: lfvdm_gn_bwd_ws_floats(C0 + C1, N, P) floats of scratch; 0 means the slice is small
- * and the single-workgroup kernels (lfvdm_gn_bwd_fused / _stats + _apply) are the ones to call.  dx is written (not
- * accumulated) to out0 / out1 with add / add2 folded in.  The per-(sample, channel) sums go to sums_out[N][C][2] when it is
- * not NULL (fixed order: deterministic mode, autograd delivery) and / or - dgamma, dbeta not NULL - into the parameter /
- * FiLM gradients with float atomics exactly as lfvdm_gn_bwd_fused does.  dx itself is deterministic either way. */
+/* lfvdm_gn_bwd_stats + _apply (+ the parameter gradients) as ONE call for every map size: the training path.  dx is
+ * WRITTEN (never accumulated) to out0 / out1 with add / add2 folded in: optional rows [N*P][add_ld] / [N*P][add2_ld]
+ * (strides >= C0+C1, multiples of 4) of further gradients of the same input - the skip path of a ResBlock, what the
+ * decoder's skip connection sends back to an encoder output.  The per-(sample, channel) sums go to EXACTLY ONE
+ * destination (both or neither: LFVDM_E_SHAPE):
+ *   - sums_out[N][C][2], each pair stored by exactly one workgroup: the fixed-order choice (deterministic mode, autograd
+ *     delivery); lfvdm_gn_param_grads or the caller reduces them in sample order;
+ *   - dgamma / dbeta [C] and - film != NULL - dfilm [N/T][2C] (zero it first), ACCUMULATED with float atomics (same sums
+ *     as lfvdm_gn_param_grads, order not fixed).  gamma, beta, film, film_ld, T, dfilm, dfilm_ld are read only here.
+ * ws: lfvdm_gn_bwd_ws_floats(C0 + C1, N, P) floats of scratch.  0 means the (sample, 8 groups) slice is small: one launch
+ * of N*4 workgroups, ws may be NULL.  Otherwise the large-map form (what lfvdm_gn_apply_ws is to the forward; pixel-space
+ * maps, N <= 65535): a workgroup owns a chunk of positions of a slice, chunk sums into ws -> fixed-order combination in
+ * every consumer workgroup -> dx: two launches of thousands of workgroups.  dx itself is deterministic either way.
+ * Pointers, then the 64-bit field, then ten 32-bit fields: 192 bytes with no implicit padding (so no pad field). */
+typedef struct lfvdm_gn_bwd_args {
+    const float* da;         /* [N*P][C0+C1] gradient w.r.t. act(x*A+B) */
+    const float* src0;       /* x as a virtual concat [N][P][C0 | C1]; src1 / out1 may be NULL when C1 == 0 */
+    const float* src1;
+    const float* coefA;      /* coefA / coefB [N][C], stats [N][32][2]: what lfvdm_gn_coef_stats wrote */
+    const float* coefB;
+    const float* stats;
+    float* out0;
+    float* out1;
+    const float* add;
+    const float* add2;
+    const float* gamma;
+    const float* beta;
+    const float* film;       /* [N/T][film_ld] rows (scale | shift) or NULL; dfilm [N/T][dfilm_ld] likewise */
+    float* dgamma;
+    float* dbeta;
+    float* dfilm;
+    float* sums_out;
+    float* ws;
+    int64_t ws_floats;
+    int32_t C0, C1, N, P, act;
+    int32_t add_ld, add2_ld, film_ld, T, dfilm_ld;       /* T: samples per FiLM row (n = b*T + t) */
+} lfvdm_gn_bwd_args;
 long lfvdm_gn_bwd_ws_floats(int C, int N, int P);
-int lfvdm_gn_bwd_ws(const float* da, const float* src0, const float* src1, int C0, int C1, int N, int P,
-                    const float* coefA, const float* coefB, const float* stats, int act, float* out0, float* out1,
-                    const float* gamma, const float* beta, const float* film, int film_ld, int T, float* dgamma,
-                    float* dbeta, float* dfilm, int dfilm_ld, const float* add, int add_ld, const float* add2, int add2_ld,
-                    float* sums_out, float* ws, long ws_floats, void* stream);
+int lfvdm_gn_bwd(const lfvdm_gn_bwd_args* a, void* stream);
 /* GroupNorm(+FiLM) parameter gradients from the sums of lfvdm_gn_bwd_stats: dgamma / dbeta [C] are ACCUMULATED
  * (+=, fixed order), dfilm [N/T][2C] (d scale | d shift of unet.py:199-203; row strides film_ld / dfilm_ld) is
  * written when film != NULL. */

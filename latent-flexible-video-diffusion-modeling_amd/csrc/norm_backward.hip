@@ -849,75 +849,57 @@ extern "C" int lfvdm_gn_bwd_apply_params(const float* da, const float* src0, con
     return LFVDM_OK;
 }
 
-extern "C" int lfvdm_gn_bwd_fused(const float* da, const float* src0, const float* src1, int C0, int C1, int N, int P,
-                                  const float* coefA, const float* coefB, const float* stats, int act, float* out0,
-                                  float* out1, const float* gamma, const float* beta, const float* film, int film_ld, int T,
-                                  float* dgamma, float* dbeta, float* dfilm, int dfilm_ld, const float* add, int add_ld,
-                                  const float* add2, int add2_ld, void* stream) {
-    const int C = C0 + C1;
-    if (N <= 0 || P <= 0 || C <= 0 || C % 32 || C0 % 4 || C > 1024) return LFVDM_E_SHAPE;
-    if (C1 > 0 && (!src1 || !out1)) return LFVDM_E_SHAPE;
-    if (!dgamma || !dbeta) return LFVDM_E_SHAPE;
-    if (add && (add_ld < C || add_ld % 4)) return LFVDM_E_SHAPE;
-    if (add2 && (add2_ld < C || add2_ld % 4)) return LFVDM_E_SHAPE;
-    if (film && (!gamma || !beta || !dfilm || T <= 0 || N % T || film_ld < 2 * C || dfilm_ld < 2 * C)) return LFVDM_E_SHAPE;
-    const GnParamGradArgs pg = {gamma, beta, film, dgamma, dbeta, dfilm, film_ld, dfilm_ld, T > 0 ? T : 1, add, add_ld, add2, add2_ld};
-    hipLaunchKernelGGL(gn_bwd_fused_kernel, dim3(N, 32 / GB_GPW), dim3(GB_THREADS), 0, (hipStream_t)stream, da, src0, src1,
-                       C0, C1, P, coefA, coefB, stats, act, out0, out1, pg, (float*)nullptr);
-    LFVDM_CHECK_LAUNCH();
-    return LFVDM_OK;
-}
-
-extern "C" int lfvdm_gn_bwd_fused_sums(const float* da, const float* src0, const float* src1, int C0, int C1, int N, int P,
-                                       const float* coefA, const float* coefB, const float* stats, int act, float* out0,
-                                       float* out1, const float* add, int add_ld, const float* add2, int add2_ld, float* sums,
-                                       void* stream) {
-    const int C = C0 + C1;
-    if (N <= 0 || P <= 0 || C <= 0 || C % 32 || C0 % 4 || C > 1024 || !sums) return LFVDM_E_SHAPE;
-    if (C1 > 0 && (!src1 || !out1)) return LFVDM_E_SHAPE;
-    if (add && (add_ld < C || add_ld % 4)) return LFVDM_E_SHAPE;
-    if (add2 && (add2_ld < C || add2_ld % 4)) return LFVDM_E_SHAPE;
-    const GnParamGradArgs pg = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 1, add, add_ld, add2, add2_ld};
-    hipLaunchKernelGGL(gn_bwd_fused_kernel, dim3(N, 32 / GB_GPW), dim3(GB_THREADS), 0, (hipStream_t)stream, da, src0, src1,
-                       C0, C1, P, coefA, coefB, stats, act, out0, out1, pg, sums);
-    LFVDM_CHECK_LAUNCH();
-    return LFVDM_OK;
+// What lfvdm_gn_bwd launches, and what lfvdm_gn_bwd_ws_floats therefore asks for: chunks per (sample, 8 groups) slice, 0 =
+// the single-workgroup kernel (small slices; any slice under the A/B switch).  C: a multiple of 32.
+static int gn_bwd_plan(int C, int P, int* pl_out) {
+    static const bool off = getenv("LFVDM_GN_BWD_NO_CHUNKS") != nullptr;       // A/B aid
+    return off ? 0 : gn_bwd_chunks(C, P, pl_out);
 }
 
 extern "C" long lfvdm_gn_bwd_ws_floats(int C, int N, int P) {
     if (C <= 0 || C % 32 || C > 1024 || N <= 0 || P <= 0) return 0;
-    static const bool off = getenv("LFVDM_GN_BWD_NO_CHUNKS") != nullptr;       // A/B aid
-    if (off) return 0;
-    const int S = gn_bwd_chunks(C, P, nullptr);
-    return (long)N * S * C * 2;
+    return (long)N * gn_bwd_plan(C, P, nullptr) * C * 2;
 }
 
-extern "C" int lfvdm_gn_bwd_ws(const float* da, const float* src0, const float* src1, int C0, int C1, int N, int P,
-                               const float* coefA, const float* coefB, const float* stats, int act, float* out0,
-                               float* out1, const float* gamma, const float* beta, const float* film, int film_ld, int T,
-                               float* dgamma, float* dbeta, float* dfilm, int dfilm_ld, const float* add, int add_ld,
-                               const float* add2, int add2_ld, float* sums_out, float* ws, long ws_floats, void* stream) {
-    const int C = C0 + C1;
-    if (N <= 0 || P <= 0 || C <= 0 || C % 32 || C0 % 4 || C > 1024 || N > 65535) return LFVDM_E_SHAPE;
-    if (C1 > 0 && (!src1 || !out1)) return LFVDM_E_SHAPE;
-    if (!da || !src0 || !out0 || !coefA || !coefB || !stats) return LFVDM_E_SHAPE;
-    if ((dgamma == nullptr) != (dbeta == nullptr)) return LFVDM_E_SHAPE;
-    if (!dgamma && !sums_out) return LFVDM_E_SHAPE;          // the per-channel sums must go somewhere
-    if (add && (add_ld < C || add_ld % 4)) return LFVDM_E_SHAPE;
-    if (add2 && (add2_ld < C || add2_ld % 4)) return LFVDM_E_SHAPE;
-    if (dgamma && film && (!gamma || !beta || !dfilm || T <= 0 || N % T || film_ld < 2 * C || dfilm_ld < 2 * C)) return LFVDM_E_SHAPE;
-    int PL = 0;
-    const int S = gn_bwd_chunks(C, P, &PL);
-    if (S == 0 || !ws || ws_floats < (long)N * S * C * 2) return LFVDM_E_SHAPE;
-    const GnBwdChunkGeom g = {C0, C1, P, S, PL};
-    const GnParamGradArgs pg = {gamma, beta, dgamma ? film : nullptr, dgamma, dbeta, dfilm, film_ld, dfilm_ld, T > 0 ? T : 1,
-                                add, add_ld, add2, add2_ld};
-    const dim3 grid(S, 32 / GB_GPW, N);
-    hipLaunchKernelGGL(gn_bwd_chunk_stats_kernel, grid, dim3(GB_THREADS), 0, (hipStream_t)stream, da, src0, src1, g, coefA, coefB,
-                       stats, act, ws);
+// Every refusal of lfvdm_gn_bwd, before anything is launched.  On LFVDM_OK *g holds the launch geometry (S = 0: the
+// single-workgroup kernel).
+static int gn_bwd_check(const lfvdm_gn_bwd_args* a, GnBwdChunkGeom* g) {
+    if (!a) return LFVDM_E_SHAPE;
+    const int C = a->C0 + a->C1;
+    if (a->N <= 0 || a->P <= 0 || a->C0 < 0 || a->C1 < 0 || C <= 0 || C % 32 || a->C0 % 4 || C > 1024) return LFVDM_E_SHAPE;
+    if (!a->da || !a->src0 || !a->out0 || !a->coefA || !a->coefB || !a->stats) return LFVDM_E_SHAPE;
+    if (a->C1 > 0 && (!a->src1 || !a->out1)) return LFVDM_E_SHAPE;
+    if (a->add && (a->add_ld < C || a->add_ld % 4)) return LFVDM_E_SHAPE;
+    if (a->add2 && (a->add2_ld < C || a->add2_ld % 4)) return LFVDM_E_SHAPE;
+    if ((a->dgamma == nullptr) != (a->dbeta == nullptr)) return LFVDM_E_SHAPE;
+    if ((a->dgamma != nullptr) == (a->sums_out != nullptr)) return LFVDM_E_SHAPE;      // the sums go to exactly one place
+    if (a->dgamma && a->film && (!a->gamma || !a->beta || !a->dfilm || a->T <= 0 || a->N % a->T || a->film_ld < 2 * C ||
+                                 a->dfilm_ld < 2 * C))
+        return LFVDM_E_SHAPE;
+    *g = {a->C0, a->C1, a->P, 0, 0};
+    g->S = gn_bwd_plan(C, a->P, &g->PL);
+    if (g->S > 0 && (a->N > 65535 || !a->ws || a->ws_floats < (int64_t)a->N * g->S * C * 2)) return LFVDM_E_SHAPE;   // N: grid z
+    return LFVDM_OK;
+}
+
+extern "C" int lfvdm_gn_bwd(const lfvdm_gn_bwd_args* a, void* stream) {
+    GnBwdChunkGeom g;
+    if (const int rc = gn_bwd_check(a, &g)) return rc;
+    const int C0 = a->C0, C1 = a->C1, N = a->N, P = a->P;
+    const GnParamGradArgs pg = {a->gamma, a->beta, a->dgamma ? a->film : nullptr, a->dgamma, a->dbeta, a->dfilm, a->film_ld,
+                                a->dfilm_ld, a->T > 0 ? a->T : 1, a->add, a->add_ld, a->add2, a->add2_ld};
+    if (g.S == 0) {
+        hipLaunchKernelGGL(gn_bwd_fused_kernel, dim3(N, 32 / GB_GPW), dim3(GB_THREADS), 0, (hipStream_t)stream, a->da, a->src0,
+                           a->src1, C0, C1, P, a->coefA, a->coefB, a->stats, a->act, a->out0, a->out1, pg, a->sums_out);
+        LFVDM_CHECK_LAUNCH();
+        return LFVDM_OK;
+    }
+    const dim3 grid(g.S, 32 / GB_GPW, N);
+    hipLaunchKernelGGL(gn_bwd_chunk_stats_kernel, grid, dim3(GB_THREADS), 0, (hipStream_t)stream, a->da, a->src0, a->src1, g,
+                       a->coefA, a->coefB, a->stats, a->act, a->ws);
     LFVDM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_bwd_chunk_apply_kernel, grid, dim3(GB_THREADS), 0, (hipStream_t)stream, da, src0, src1, g, coefA, coefB,
-                       stats, act, (const float*)ws, out0, out1, pg, sums_out);
+    hipLaunchKernelGGL(gn_bwd_chunk_apply_kernel, grid, dim3(GB_THREADS), 0, (hipStream_t)stream, a->da, a->src0, a->src1, g,
+                       a->coefA, a->coefB, a->stats, a->act, (const float*)a->ws, a->out0, a->out1, pg, a->sums_out);
     LFVDM_CHECK_LAUNCH();
     return LFVDM_OK;
 }

@@ -8,7 +8,8 @@ HIP kernels for the heavy work of the reference's ``loss.backward()`` (train_uti
     the zero-insertion gather), weight/bias gradient ``lfvdm_conv_wgrad`` (fp32 MFMA, the fused
     GroupNorm/FiLM/SiLU operand is recomputed on the fly, never stored);
   * GroupNorm(+FiLM)(+SiLU): ``lfvdm_gn_apply`` forward (normalised + activated tensor materialised once and
-    saved: it is the raw operand of the GEMM and of the weight-gradient kernel), ``lfvdm_gn_bwd_stats/apply`` backward;
+    saved: it is the raw operand of the GEMM and of the weight-gradient kernel), ``lfvdm_gn_bwd`` backward (autograd
+    delivery on small maps: ``lfvdm_gn_bwd_stats/apply``);
     temporal GroupNorm ``lfvdm_gn_temporal(_bwd)``;
   * attention cores: forward ``lfvdm_attn_spatial`` (saves the log-sum-exp) / ``lfvdm_attn_temporal``, backward
     ``lfvdm_attn_spatial_bwd`` (flash style dq / dk,dv kernels) and ``lfvdm_attn_temporal_bwd`` (rows / cols /
@@ -466,93 +467,51 @@ def _gn_forward(a, b, C0, C1, N, P, gamma, beta, film, T):
 def _gn_backward(da, a, b, C0, C1, N, P, cA, cB, stats, act, gamma, beta, film, T, want_dx=(True, True), dfilm_out=None,
                  inplace=False, add=None, add2=None):
     """Returns (dx_a, dx_b, dgamma, dbeta, dfilm).  da: [N*P][C] gradient w.r.t. act(GN(x)).  add, add2: optional
-    [N*P][C] rows (further gradients of the same input) folded into dx by the in-place kernel."""
+    [N*P][C] rows (further gradients of the same input) folded into dx by the in-place kernel.  Three delivery modes of
+    the parameter / FiLM gradients: in place with float atomics (the training default: everything in lfvdm_gn_bwd), in
+    place with a fixed summation order (LFVDM_DETERMINISTIC: per-(sample, channel) sums -> lfvdm_gn_param_grads, which
+    walks the samples in order), autograd (sums -> torch reductions, returned)."""
     C = C0 + C1
     if add2 is not None and not inplace:
         add, add2 = (add2 if add is None else add + add2), None
-    (p_add, ld_add), (p_add2, ld_add2) = _rows(add), _rows(add2)
     L = nat.lib()
     dxa = _new(N * P, C0, like=da)
     dxb = _new(N * P, C1, like=da) if C1 else None
-    need = int(L.lfvdm_gn_bwd_ws_floats(C, N, P))
-    if need:
-        # large map (pixel space, wide concats at 32x32): chunked two-launch form, thousands of workgroups
-        return _gn_backward_chunked(da, a, b, C0, C1, N, P, cA, cB, stats, act, gamma, beta, film, T, dfilm_out, inplace, add,
-                                    add2, dxa, dxb, need)
-    if inplace and nat.deterministic():
-        # fixed summation order: per-(sample, channel) sums (lfvdm_gn_bwd_stats), dx (lfvdm_gn_bwd_apply), then the
-        # parameter / FiLM gradients by lfvdm_gn_param_grads, which walks the samples in order - no float atomics
-        # (the statistics + dx launch is the training path's fused kernel, with the sums stored instead of added)
-        sums = _new(N, C, 2, like=da)
-        nat.check(L.lfvdm_gn_bwd_fused_sums(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
-                                            act, nat.ptr(dxa), nat.ptr(dxb), p_add, ld_add, p_add2, ld_add2, nat.ptr(sums), nat.stream()),
-                  "lfvdm_gn_bwd_fused_sums")
-        dfilm = None
-        if film is not None:
-            dfilm = dfilm_out if dfilm_out is not None else th.zeros(N // T, 2 * C, device=da.device, dtype=th.float32)
-        nat.check(L.lfvdm_gn_param_grads(nat.ptr(sums), nat.ptr(gamma), nat.ptr(beta), film.data_ptr() if film is not None else None,
-                                         film.stride(0) if film is not None else 0, T, nat.ptr(_grad_of(gamma)), nat.ptr(_grad_of(beta)),
-                                         dfilm.data_ptr() if dfilm is not None else None, dfilm.stride(0) if dfilm is not None else 0,
-                                         N, C, nat.stream()), "lfvdm_gn_param_grads")
-        return dxa, dxb, None, None, (None if dfilm_out is not None else dfilm)
-    if inplace:
-        # statistics, dx and the parameter gradients in ONE launch (float atomics into .grad / the FiLM gradient slot)
-        dfilm = None
-        if film is not None:       # accumulated into the caller's (zeroed) slot of the embedding network's gradient buffer
-            dfilm = dfilm_out if dfilm_out is not None else th.zeros(N // T, 2 * C, device=da.device, dtype=th.float32)
-        nat.check(L.lfvdm_gn_bwd_fused(
-            nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats), act,
-            nat.ptr(dxa), nat.ptr(dxb), nat.ptr(gamma), nat.ptr(beta),
-            film.data_ptr() if film is not None else None, film.stride(0) if film is not None else 0, T,
-            nat.ptr(_grad_of(gamma)), nat.ptr(_grad_of(beta)), dfilm.data_ptr() if dfilm is not None else None,
-            dfilm.stride(0) if dfilm is not None else 0, p_add, ld_add, p_add2, ld_add2, nat.stream()), "lfvdm_gn_bwd_fused")
-        return dxa, dxb, None, None, (None if dfilm_out is not None else dfilm)
-    sums = _new(N, C, 2, like=da)
-    nat.check(L.lfvdm_gn_bwd_stats(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
-                                   act, nat.ptr(sums), nat.stream()), "lfvdm_gn_bwd_stats")
-    nat.check(L.lfvdm_gn_bwd_apply(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
-                                   nat.ptr(sums), act, nat.ptr(dxa), nat.ptr(dxb), 0, 0, nat.stream()), "lfvdm_gn_bwd_apply")
-    if add is not None:
-        dxa = dxa + add[:, :C0]
-        if dxb is not None:
-            dxb = dxb + add[:, C0:]
-    assert dfilm_out is None, "gradient slots belong to the in-place mode"
-    dgamma, dbeta, dfilm = _gn_param_grads_torch(sums, gamma, beta, film, T, N, C)
-    return dxa, dxb, dgamma, dbeta, dfilm
-
-
-def _gn_backward_chunked(da, a, b, C0, C1, N, P, cA, cB, stats, act, gamma, beta, film, T, dfilm_out, inplace, add, add2,
-                         dxa, dxb, need):
-    """lfvdm_gn_bwd_ws for all three delivery modes: in place with float atomics (the training default), in place with a
-    fixed summation order (LFVDM_DETERMINISTIC: per-(sample, channel) sums -> lfvdm_gn_param_grads), autograd (sums ->
-    torch reductions).  (add2 has already been folded into add by the caller unless the kernel takes both.)"""
-    C = C0 + C1
-    L = nat.lib()
-    ws = _new(need, like=da)
+    need = int(L.lfvdm_gn_bwd_ws_floats(C, N, P))          # > 0: large map (pixel space, wide concats at 32x32), chunked form
     atomics = inplace and not nat.deterministic()
     sums = None if atomics else _new(N, C, 2, like=da)
+    assert inplace or dfilm_out is None, "gradient slots belong to the in-place mode"
+    if not need and not inplace:
+        # small map, autograd delivery: the two-pass primitives
+        nat.check(L.lfvdm_gn_bwd_stats(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
+                                       act, nat.ptr(sums), nat.stream()), "lfvdm_gn_bwd_stats")
+        nat.check(L.lfvdm_gn_bwd_apply(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
+                                       nat.ptr(sums), act, nat.ptr(dxa), nat.ptr(dxb), 0, 0, nat.stream()), "lfvdm_gn_bwd_apply")
+        if add is not None:
+            dxa = dxa + add[:, :C0]
+            if dxb is not None:
+                dxb = dxb + add[:, C0:]
+        return (dxa, dxb) + _gn_param_grads_torch(sums, gamma, beta, film, T, N, C)
     dfilm = None
-    if film is not None and inplace:
+    if film is not None and inplace:    # the caller's (zeroed) slot of the embedding network's gradient buffer, or a fresh one
         dfilm = dfilm_out if dfilm_out is not None else th.zeros(N // T, 2 * C, device=da.device, dtype=th.float32)
-    fptr = film.data_ptr() if film is not None else None
-    fld = film.stride(0) if film is not None else 0
+    fptr, fld = (film.data_ptr(), film.stride(0)) if film is not None else (None, 0)
+    dfptr, dfld = (dfilm.data_ptr(), dfilm.stride(0)) if dfilm is not None else (None, 0)
+    ws = _new(need, like=da) if need else None
     (p_add, ld_add), (p_add2, ld_add2) = _rows(add), _rows(add2)
-    nat.check(L.lfvdm_gn_bwd_ws(
-        nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats), act, nat.ptr(dxa),
-        nat.ptr(dxb), nat.ptr(gamma), nat.ptr(beta), fptr if atomics else None, fld, T,
-        nat.ptr(_grad_of(gamma)) if atomics else None, nat.ptr(_grad_of(beta)) if atomics else None,
-        dfilm.data_ptr() if (atomics and dfilm is not None) else None, dfilm.stride(0) if dfilm is not None else 0,
-        p_add, ld_add, p_add2, ld_add2, nat.ptr(sums), nat.ptr(ws), need, nat.stream()), "lfvdm_gn_bwd_ws")
-    if atomics:
-        return dxa, dxb, None, None, (None if dfilm_out is not None else dfilm)
-    if inplace:
+    args = nat.GnBwdArgs(da=nat.ptr(da), src0=nat.ptr(a), src1=nat.ptr(b), C0=C0, C1=C1, N=N, P=P, coefA=nat.ptr(cA),
+                         coefB=nat.ptr(cB), stats=nat.ptr(stats), act=act, out0=nat.ptr(dxa), out1=nat.ptr(dxb), add=p_add,
+                         add_ld=ld_add, add2=p_add2, add2_ld=ld_add2, sums_out=nat.ptr(sums), ws=nat.ptr(ws), ws_floats=need)
+    if atomics:     # the kernel adds into .grad / the FiLM gradient slot; otherwise it stores the sums
+        args.gamma, args.beta, args.film, args.film_ld, args.T = nat.ptr(gamma), nat.ptr(beta), fptr, fld, T
+        args.dgamma, args.dbeta, args.dfilm, args.dfilm_ld = nat.ptr(_grad_of(gamma)), nat.ptr(_grad_of(beta)), dfptr, dfld
+    nat.check(L.lfvdm_gn_bwd(ctypes.byref(args), nat.stream()), "lfvdm_gn_bwd")
+    if not inplace:
+        return (dxa, dxb) + _gn_param_grads_torch(sums, gamma, beta, film, T, N, C)
+    if not atomics:
         nat.check(L.lfvdm_gn_param_grads(nat.ptr(sums), nat.ptr(gamma), nat.ptr(beta), fptr, fld, T, nat.ptr(_grad_of(gamma)),
-                                         nat.ptr(_grad_of(beta)), dfilm.data_ptr() if dfilm is not None else None,
-                                         dfilm.stride(0) if dfilm is not None else 0, N, C, nat.stream()), "lfvdm_gn_param_grads")
-        return dxa, dxb, None, None, (None if dfilm_out is not None else dfilm)
-    assert dfilm_out is None, "gradient slots belong to the in-place mode"
-    dgamma, dbeta, dfilm = _gn_param_grads_torch(sums, gamma, beta, film, T, N, C)
-    return dxa, dxb, dgamma, dbeta, dfilm
+                                         nat.ptr(_grad_of(beta)), dfptr, dfld, N, C, nat.stream()), "lfvdm_gn_param_grads")
+    return dxa, dxb, None, None, (None if dfilm_out is not None else dfilm)
 
 
 def _gn_param_grads_torch(sums, gamma, beta, film, T, N, C):

@@ -47,6 +47,13 @@ class GnArgs(C.Structure):
                 ("out_col", C.c_int32), ("pad_", C.c_int32)]
 
 
+class GnBwdArgs(C.Structure):
+    """lfvdm_gn_bwd_args (include/lfvdm_hip.h): the fused spatial GroupNorm backward."""
+    _fields_ = ([(n, c_fp) for n in ("da", "src0", "src1", "coefA", "coefB", "stats", "out0", "out1", "add", "add2", "gamma", "beta",
+                                     "film", "dgamma", "dbeta", "dfilm", "sums_out", "ws")] + [("ws_floats", C.c_int64)]
+                + [(n, C.c_int32) for n in ("C0", "C1", "N", "P", "act", "add_ld", "add2_ld", "film_ld", "T", "dfilm_ld")])
+
+
 class ChainStage(C.Structure):
     """lfvdm_chain_stage (include/lfvdm_hip.h): one stage of a persistent level chain."""
     _fields_ = [("kind", C.c_int32), ("n_items", C.c_int32), ("flag_base", C.c_int32), ("n_flags", C.c_int32),
@@ -146,13 +153,8 @@ _SIGS = {
     "lfvdm_gn_bwd_apply": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_bwd_apply_params": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i,
                                    c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_i, c_fp], c_i),
-    "lfvdm_gn_bwd_fused_sums": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_i,
-                                 c_fp, c_fp], c_i),
     "lfvdm_gn_bwd_ws_floats": ([c_i, c_i, c_i], C.c_long),
-    "lfvdm_gn_bwd_ws": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i,
-                         c_fp, c_fp, c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp, c_fp, C.c_long, c_fp], c_i),
-    "lfvdm_gn_bwd_fused": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i,
-                            c_fp, c_fp, c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp], c_i),
+    "lfvdm_gn_bwd": ([C.POINTER(GnBwdArgs), c_fp], c_i),
     "lfvdm_gn_param_grads": ([c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_rowdot_bwd": ([c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_temporal_bwd": ([c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp], c_i),

@@ -111,6 +111,78 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.lfvdm_abi_version() == 9
 
 
+def _header_struct_layout(hdr, name):
+    """[(field, offset)] and sizeof of a header struct of pointers, int64_t and int32_t, by natural alignment."""
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields, off = [], 0
+    for decl in (" ".join(d.split()) for d in body.split(";") if d.strip()):
+        m = re.fullmatch(r"(const float\*|float\*|int64_t|int32_t) (\w+(?:, \w+)*)", decl)
+        assert m, decl
+        size = 4 if m.group(1) == "int32_t" else 8
+        for field in m.group(2).split(", "):
+            off = -(-off // size) * size
+            fields.append((field, off))
+            off += size
+    return fields, -(-off // 8) * 8
+
+
+def test_gn_bwd_record_matches_its_binding_and_refuses_on_the_host():
+    """lfvdm_gn_bwd_args in the header and _native.GnBwdArgs: same fields in the same order, same size and offsets.  The three
+    wide entries it replaced are neither declared, bound nor exported.  Every refusal of lfvdm_gn_bwd happens before a
+    launch, so it is checked here without a device (the pointers are never read on the host)."""
+    from improved_diffusion import _native as nat
+    hdr = open(os.path.join(ROOT, "include", "lfvdm_hip.h")).read()
+    fields, size = _header_struct_layout(hdr, "lfvdm_gn_bwd_args")
+    assert [(n, getattr(nat.GnBwdArgs, n).offset) for n, _ in nat.GnBwdArgs._fields_] == fields
+    assert ctypes.sizeof(nat.GnBwdArgs) == size == 192
+    assert {n for n, _ in fields} == {
+        "da", "src0", "src1", "C0", "C1", "N", "P", "coefA", "coefB", "stats", "act", "out0", "out1", "add", "add_ld", "add2",
+        "add2_ld", "gamma", "beta", "film", "film_ld", "T", "dgamma", "dbeta", "dfilm", "dfilm_ld", "sums_out", "ws", "ws_floats"}
+    declared = set(re.findall(r"\b(lfvdm_[a-z0-9_]+)\s*\(", hdr))
+    L = nat.lib()
+    for name in ("lfvdm_gn_bwd_fused", "lfvdm_gn_bwd_fused_sums", "lfvdm_gn_bwd_ws"):
+        assert name not in declared and name not in nat.EXPORTS and not hasattr(L, name), name
+    for name in ("lfvdm_gn_bwd", "lfvdm_gn_bwd_ws_floats", "lfvdm_gn_bwd_stats", "lfvdm_gn_bwd_apply", "lfvdm_gn_bwd_apply_params",
+                 "lfvdm_gn_param_grads"):
+        assert name in declared and name in nat.EXPORTS and hasattr(L, name), name
+
+    host = (ctypes.c_float * 4)()
+    p = ctypes.addressof(host)              # stands for a device pointer: a refused call reads none of them
+    C0, C1, N = 64, 32, 2
+    small, chunked = 4, 16 * (256 // (2 * (C0 + C1) // 32)) + 1
+    assert L.lfvdm_gn_bwd_ws_floats(C0 + C1, N, small) == 0
+    need = L.lfvdm_gn_bwd_ws_floats(C0 + C1, N, chunked)
+    assert need > 0
+
+    def rc(P=small, **kw):
+        a = dict(da=p, src0=p, src1=p, coefA=p, coefB=p, stats=p, out0=p, out1=p, C0=C0, C1=C1, N=N, P=P, act=1, sums_out=p)
+        a.update(kw)
+        return L.lfvdm_gn_bwd(ctypes.byref(nat.GnBwdArgs(**a)), None)
+
+    atomics = dict(sums_out=None, gamma=p, beta=p, dgamma=p, dbeta=p)
+    refused = {
+        "C % 32": rc(C0=48, C1=0), "C0 % 4": rc(C0=30, C1=2), "C > 1024": rc(C0=1056, C1=0), "C > 1024 (concat)": rc(C0=1024, C1=32),
+        "C0 < 0": rc(C0=-32, C1=64), "N = 0": rc(N=0), "P = 0": rc(P=0),
+        "no src1": rc(src1=None), "no out1": rc(out1=None),
+        **{f"no {k}": rc(**{k: None}) for k in ("da", "src0", "out0", "coefA", "coefB", "stats")},
+        "add_ld < C": rc(add=p, add_ld=92), "add_ld % 4": rc(add=p, add_ld=98),
+        "add2_ld < C": rc(add2=p, add2_ld=92), "add2_ld % 4": rc(add2=p, add2_ld=98),
+        "atomics, add_ld < C": rc(**atomics, add=p, add_ld=92), "atomics, add2_ld < C": rc(**atomics, add2=p, add2_ld=92),
+        "neither destination": rc(sums_out=None), "both destinations": rc(**dict(atomics, sums_out=p)),
+        "dgamma without dbeta": rc(**dict(atomics, dbeta=None)),
+        "film without dfilm": rc(**atomics, film=p, film_ld=192, T=1, dfilm_ld=192),
+        "film, N % T": rc(**atomics, film=p, film_ld=192, T=3, dfilm=p, dfilm_ld=192),
+        "film_ld < 2C": rc(**atomics, film=p, film_ld=188, T=1, dfilm=p, dfilm_ld=192),
+        "dfilm_ld < 2C": rc(**atomics, film=p, film_ld=192, T=1, dfilm=p, dfilm_ld=188),
+        "chunked, ws = NULL": rc(P=chunked, ws=None, ws_floats=need),
+        "chunked, short ws": rc(P=chunked, ws=p, ws_floats=need - 1),
+        "chunked, N = 65536": rc(P=chunked, N=65536, ws=p, ws_floats=L.lfvdm_gn_bwd_ws_floats(C0 + C1, 65536, chunked)),
+        "NULL record": L.lfvdm_gn_bwd(None, None),
+    }
+    assert refused == dict.fromkeys(refused, 1), {k: v for k, v in refused.items() if v != 1}
+
+
 def _loop_stub(max_frames=6, pad=True):
     from improved_diffusion.train_util import TrainLoop
     loop = TrainLoop.__new__(TrainLoop)

@@ -1,8 +1,8 @@
 """Op-level fp64 parity of the GroupNorm backward kernels and of the deterministic (ordered-slab) gradient entry points.
 
-- the small-slice spatial GroupNorm(+FiLM)(+SiLU) backward (lfvdm_gn_bwd_fused, _fused_sums + lfvdm_gn_param_grads,
-  _stats + _apply, _apply_params) through _backward._gn_backward in its three delivery modes, at every channel split the
-  models use, on both sides of the small / chunked boundary;
+- the small-slice spatial GroupNorm(+FiLM)(+SiLU) backward (lfvdm_gn_bwd with either destination of the sums,
+  lfvdm_gn_param_grads, _stats + _apply, _apply_params) through _backward._gn_backward in its three delivery modes, at every
+  channel split the models use, on both sides of the small / chunked boundary;
 - temporal GroupNorm forward and backward (atomic and _det) for every kernel the dispatch can pick, up to 64 frames;
 - lfvdm_rowdot_bwd_det and lfvdm_conv_wgrad with a slab (every tune code, every slab capacity class).
 
@@ -147,8 +147,8 @@ def _outside_slot_untouched(buf, C, canary=1234.5):
 
 @pytest.mark.parametrize("C0,C1,pcls,N,T,act,film,adds", SMALL_SLICE_CASES)
 def test_gn_backward_small_slices(nat, monkeypatch, C0, C1, pcls, N, T, act, film, adds):
-    """_backward._gn_backward in the three delivery modes (atomics: lfvdm_gn_bwd_fused; LFVDM_DETERMINISTIC=1:
-    lfvdm_gn_bwd_fused_sums + lfvdm_gn_param_grads; autograd: lfvdm_gn_bwd_stats + lfvdm_gn_bwd_apply) vs fp64 autograd:
+    """_backward._gn_backward in the three delivery modes (atomics: lfvdm_gn_bwd; LFVDM_DETERMINISTIC=1: lfvdm_gn_bwd storing
+    the sums + lfvdm_gn_param_grads; autograd: lfvdm_gn_bwd_stats + lfvdm_gn_bwd_apply) vs fp64 autograd:
     ragged position loops, idle lanes (C/32 = 3, 6, 12, 24), 4-channel vectors across group and concat boundaries, add /
     add2 rows with a stride wider than C, accumulation into preloaded .grad, the FiLM gradient in a strided slot with
     canaries.  dx is bitwise the same in the atomic and deterministic modes (same kernel) and bitwise repeatable everywhere;
@@ -248,7 +248,8 @@ def test_gn_backward_small_slices(nat, monkeypatch, C0, C1, pcls, N, T, act, fil
 
 
 def test_gn_backward_small_slice_refusals(nat):
-    """Every single-workgroup entry point refuses C % 32 != 0, C0 % 4 != 0, C > 1024 and (where it takes one) add_ld < C."""
+    """Every single-workgroup entry point, and lfvdm_gn_bwd with either destination of the sums, refuses C % 32 != 0,
+    C0 % 4 != 0, C > 1024 and (where it takes one) add_ld / add2_ld < C."""
     L, s = nat.lib(), nat.stream()
     big = torch.zeros(1 << 16, device="cuda")       # large enough for every shape below (nothing may launch anyway)
     p = big.data_ptr()
@@ -264,19 +265,24 @@ def test_gn_backward_small_slice_refusals(nat):
         return L.lfvdm_gn_bwd_apply_params(p, p, p, C0, C1, N, P, p, p, p, p, 1, p, p, 0, 0, p, p, None, 0, 1, p, p, None, 0,
                                            p, add_ld, s)
 
+    def record(C0, C1, **kw):
+        a = dict(da=p, src0=p, src1=p, coefA=p, coefB=p, stats=p, out0=p, out1=p, C0=C0, C1=C1, N=N, P=P, act=1)
+        a.update(kw)
+        return L.lfvdm_gn_bwd(C.byref(nat.GnBwdArgs(**a)), s)
+
+    atomics = dict(gamma=p, beta=p, dgamma=p, dbeta=p)
+
     def fused(C0, C1, add_ld):
-        return L.lfvdm_gn_bwd_fused(p, p, p, C0, C1, N, P, p, p, p, 1, p, p, p, p, None, 0, 1, p, p, None, 0, p, add_ld,
-                                    None, 0, s)
+        return record(C0, C1, **atomics, add=p, add_ld=add_ld)
 
     def fused_add2(C0, C1, add_ld):
-        return L.lfvdm_gn_bwd_fused(p, p, p, C0, C1, N, P, p, p, p, 1, p, p, p, p, None, 0, 1, p, p, None, 0, None, 0,
-                                    p, add_ld, s)
+        return record(C0, C1, **atomics, add2=p, add2_ld=add_ld)
 
     def fused_sums(C0, C1, add_ld):
-        return L.lfvdm_gn_bwd_fused_sums(p, p, p, C0, C1, N, P, p, p, p, 1, p, p, p, add_ld, None, 0, p, s)
+        return record(C0, C1, sums_out=p, add=p, add_ld=add_ld)
 
     def fused_sums_add2(C0, C1, add_ld):
-        return L.lfvdm_gn_bwd_fused_sums(p, p, p, C0, C1, N, P, p, p, p, 1, p, p, None, 0, p, add_ld, p, s)
+        return record(C0, C1, sums_out=p, add2=p, add2_ld=add_ld)
 
     takes_add = (apply_params, fused, fused_add2, fused_sums, fused_sums_add2)
     for fn in (stats, apply) + takes_add:
@@ -286,6 +292,16 @@ def test_gn_backward_small_slice_refusals(nat):
         assert fn(64, 32, 96) == 0, fn.__name__              # the same call with a valid shape is accepted
         if fn in takes_add:
             assert fn(64, 32, 92) != 0, (fn.__name__, "add_ld < C")
+    # the record's own refusals: the sums go to exactly one destination; a chunked map needs its whole workspace and N
+    # within the grid's z dimension
+    assert record(64, 32) != 0, "neither destination"
+    assert record(64, 32, sums_out=p, **atomics) != 0, "both destinations"
+    Pc = 16 * _pl(96) + 1
+    need = L.lfvdm_gn_bwd_ws_floats(96, N, Pc)
+    assert need > 0
+    assert record(64, 32, P=Pc, sums_out=p, ws=None, ws_floats=need) != 0, "chunked map without a workspace"
+    assert record(64, 32, P=Pc, sums_out=p, ws=p, ws_floats=need - 1) != 0, "chunked map with a short workspace"
+    assert record(64, 32, N=65536, P=Pc, sums_out=p, ws=p, ws_floats=L.lfvdm_gn_bwd_ws_floats(96, 65536, Pc)) != 0, "N = 65536, chunked"
     torch.cuda.synchronize()
 
 

@@ -1,6 +1,6 @@
-"""Developer aid: per-launch time of the fused GroupNorm backward (lfvdm_gn_bwd_fused / _sums) on the cfg-C training shapes,
-50 launches per graph replay (with FiLM + atomics, atomics only, deterministic sums).  usage: python tools/gn_bwd_bench.py"""
-import os, sys
+"""Developer aid: per-call time of the fused GroupNorm backward (lfvdm_gn_bwd) on the cfg-C training shapes, 50 calls per
+graph replay (with FiLM + atomics, atomics only, deterministic sums).  usage: python tools/gn_bwd_bench.py"""
+import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "latent-flexible-video-diffusion-modeling_amd"))
 import torch as th
@@ -22,20 +22,19 @@ for C0, C1, P in shapes:
     dxa = th.empty(N * P, C0, device=dev); dxb = th.empty(N * P, C1, device=dev) if C1 else None
     add = r(N * P, C)
     sums = th.empty(N, C, 2, device=dev)
-    def atom():
-        nat.check(L.lfvdm_gn_bwd_fused(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats), 1,
-                                       nat.ptr(dxa), nat.ptr(dxb), nat.ptr(gamma), nat.ptr(beta), film.data_ptr(), film.stride(0), T,
-                                       nat.ptr(dg), nat.ptr(db), dfilm.data_ptr(), dfilm.stride(0), nat.ptr(add), add.stride(0),
-                                       None, 0, nat.stream()), "fused")
-    def nofilm():
-        nat.check(L.lfvdm_gn_bwd_fused(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats), 1,
-                                       nat.ptr(dxa), nat.ptr(dxb), nat.ptr(gamma), nat.ptr(beta), None, 0, T,
-                                       nat.ptr(dg), nat.ptr(db), None, 0, None, 0, None, 0, nat.stream()), "fused")
-    def det():
-        nat.check(L.lfvdm_gn_bwd_fused_sums(nat.ptr(da), nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats), 1,
-                                            nat.ptr(dxa), nat.ptr(dxb), nat.ptr(add), add.stride(0), None, 0, nat.ptr(sums), nat.stream()), "sums")
+    need = int(L.lfvdm_gn_bwd_ws_floats(C, N, P))
+    ws = th.empty(need, device=dev) if need else None
+    base = dict(da=nat.ptr(da), src0=nat.ptr(a), src1=nat.ptr(b), C0=C0, C1=C1, N=N, P=P, coefA=nat.ptr(cA), coefB=nat.ptr(cB),
+                stats=nat.ptr(stats), act=1, out0=nat.ptr(dxa), out1=nat.ptr(dxb), ws=nat.ptr(ws), ws_floats=need)
+    grads = dict(gamma=nat.ptr(gamma), beta=nat.ptr(beta), dgamma=nat.ptr(dg), dbeta=nat.ptr(db))
+    with_add = dict(add=nat.ptr(add), add_ld=add.stride(0))
+    variants = (("film+atomics", nat.GnBwdArgs(**base, **grads, **with_add, film=film.data_ptr(), film_ld=film.stride(0), T=T,
+                                               dfilm=dfilm.data_ptr(), dfilm_ld=dfilm.stride(0))),
+                ("atomics", nat.GnBwdArgs(**base, **grads)),
+                ("sums", nat.GnBwdArgs(**base, **with_add, sums_out=nat.ptr(sums))))
     out = []
-    for name, f in (("film+atomics", atom), ("atomics", nofilm), ("sums", det)):
+    for name, args in variants:
+        f = lambda: nat.check(L.lfvdm_gn_bwd(ctypes.byref(args), nat.stream()), name)
         s = th.cuda.Stream()
         with th.cuda.stream(s):
             for _ in range(3): f()
