@@ -800,6 +800,39 @@ int lfvdm_prepare_batch(const float* pool, const int32_t* table, float* batch, i
                         float* latent_mask, int B, int F, int Tp, int frame_elems, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Haar wavelet diffusion space (csrc/wavelet.hip; diffusion_space = "wavelet", improved_diffusion/wavelet.py).
+ *   pixels [N][C][H][W] of `dtype` LFVDM_PIX_F32 / LFVDM_PIX_U8, value = scale * raw + shift (float data in [-1, 1]: 1, 0;
+ *   uint8: 1 / 127.5, -1)  <->  coefficients [N][4^L C][H / 2^L][W / 2^L] fp32, L = levels = 1 or 2.
+ * One level maps the 2 x 2 block [[a, b], [c, d]] of a channel to ll = s (a + b + c + d), lh = s (a - b + c - d),
+ * hl = s (a + b - c - d), hh = s (a - b - c + d); s = 1/4 (LFVDM_WAVELET_RANGE: [-1, 1] stays [-1, 1]) or 1/2
+ * (LFVDM_WAVELET_ORTHONORMAL: an isometry).  L = 1: channel blocks [ll | lh | hl | hh] of C channels.  L = 2: the level is
+ * applied again to ll and the level-1 detail bands are brought to quarter resolution by space-to-depth, phase =
+ * 2 (row & 1) + (column & 1): [ll2 | lh2 | hl2 | hh2 | lh1 phases 0..3 | hl1 phases 0..3 | hh1 phases 0..3].
+ * mean / rstd (encode) and mean / std (decode): per coefficient channel [4^L C], both or neither; encode ends with
+ * (y - mean) * rstd, decode starts with y * std + mean.
+ * lfvdm_wavelet_decode writes float pixels, or uint8 as clamp(round-to-nearest((x + 1) * 127.5), 0, 255) - it ROUNDS
+ * (a cast truncates), so uint8 -> encode (1 / 127.5, -1) -> decode is the identity.
+ * lfvdm_prepare_batch_wavelet = lfvdm_prepare_batch on a pool of PIXELS [B][Tp][C][H][W] followed by lfvdm_wavelet_encode
+ * of the gathered frames, in one launch and bit for bit: same table, same clamp of a corrupt row, same index / mask outputs;
+ * batch [B][F][4^L C][H / 2^L][W / 2^L].
+ * One read of the pixels and one write of the coefficients; 16-byte (uint8: 4-byte) row accesses where W is a multiple
+ * of 4 and the base pointers are aligned, a scalar path of the same arithmetic (same bits) otherwise.
+ * A NULL pointer, one of mean / rstd without the other, a non-positive dimension, an unknown dtype or norm, H or W not a
+ * multiple of 2^L -> LFVDM_E_SHAPE; levels outside {1, 2} or more than 2^31 elements -> LFVDM_E_UNSUPPORTED; nothing is
+ * launched in either case.
+ * ------------------------------------------------------------------------------------- */
+#define LFVDM_WAVELET_RANGE 0
+#define LFVDM_WAVELET_ORTHONORMAL 1
+int lfvdm_wavelet_encode(const void* pix, int dtype, float scale, float shift, float* coef, const float* mean,
+                         const float* rstd, int N, int C, int H, int W, int levels, int norm, void* stream);
+int lfvdm_wavelet_decode(const float* coef, const float* mean, const float* std, void* pix, int dtype, int N, int C, int H,
+                         int W, int levels, int norm, void* stream);
+int lfvdm_prepare_batch_wavelet(const void* pool, int dtype, float scale, float shift, const int32_t* table, float* batch,
+                                int64_t* frame_indices, float* obs_mask, float* latent_mask, const float* mean,
+                                const float* rstd, int B, int F, int Tp, int C, int H, int W, int levels, int norm,
+                                void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Search for optimised conditioning frames (improved_diffusion/optimal_schedule.py; not in the reference).  One pass scores
  * G candidate conditioning sets on V videos as W = G * V windows of K slots; window w shows video w % V.
  *   table [W][K] int32   the video frame a slot shows, -1: padding        role [W][K] int32   LFVDM_SLOT_*

@@ -407,6 +407,12 @@ class Plan:
 
         # ---- network body
         conv0 = m.input_blocks[0][0]
+        conv_in_lds = (Cx + 1) * 9 * (ch + 4) * 4      # lfvdm_conv_in keeps its whole filter bank in LDS
+        if conv_in_lds > 64 * 1024:
+            raise NotImplementedError(
+                f"the native input convolution holds (in_channels + 1) * 9 * (model_channels + 4) floats in 64 KiB of LDS; "
+                f"in_channels={Cx} with model_channels={ch} needs {conv_in_lds} bytes.  A two-level wavelet space on RGB "
+                "(48 channels) is over that limit: use wavelet_levels=1 (12 channels, up to 128 filters)")
         h0 = self.buf(N * H * W, ch)
         self.add(L.lfvdm_conv_in, _p(self.x_in), _p(self.x0_in), _p(self.obs), _p(conv0.weight), _p(conv0.bias), _p(h0),
                  N, Cx, H, W, ch)

@@ -195,6 +195,9 @@ _SIGS = {
     "lfvdm_train_loss": ([c_fp] * 6 + [c_i] + [c_fp] * 3 + [c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_train_loss_bwd": ([c_fp] * 5 + [c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_prepare_batch": ([c_fp] * 6 + [c_i] * 4 + [c_fp], c_i),
+    "lfvdm_wavelet_encode": ([c_fp, c_i, C.c_float, C.c_float, c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp], c_i),
+    "lfvdm_wavelet_decode": ([c_fp, c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp], c_i),
+    "lfvdm_prepare_batch_wavelet": ([c_fp, c_i, C.c_float, C.c_float] + [c_fp] * 7 + [c_i] * 8 + [c_fp], c_i),
     "lfvdm_search_assemble": ([c_fp] * 9 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_search_noise_qsample": ([c_fp] * 10 + [c_i] * 4 + [c_fp], c_i),
     "lfvdm_search_noise_fill": ([c_fp, C.c_uint64, c_i, c_i, c_fp] + [c_i] * 4 + [c_fp], c_i),
@@ -793,6 +796,50 @@ def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):
     F = table.shape[1]
     check(lib().lfvdm_prepare_batch(ptr(pool), ptr(table, torch.int32), ptr(batch), ptr(frame_indices, torch.int64), ptr(obs_mask),
                                     ptr(latent_mask), B, F, Tp, pool[0, 0].numel(), stream()), "lfvdm_prepare_batch")
+
+
+WAVELET_NORMS = {"range": 0, "orthonormal": 1}
+_U8_SCALE, _U8_SHIFT = 1.0 / 127.5, -1.0      # uint8 0..255 -> [-1, 1]
+
+
+def _pix_affine(dt):
+    if dt not in _PIX:
+        raise RuntimeError(f"expected float32 or uint8 pixels, got {dt}")
+    return (_U8_SCALE, _U8_SHIFT) if dt == torch.uint8 else (1.0, 0.0)
+
+
+def wavelet_encode(pix, coef, levels, norm, mean=None, rstd=None):
+    """pix (N, C, H, W) float32 in [-1, 1] or uint8 -> coef (N, 4^L C, H / 2^L, W / 2^L) float32 (lfvdm_wavelet_encode)."""
+    N, Cc, H, W = pix.shape
+    if coef.numel() != pix.numel():
+        raise RuntimeError("wavelet_encode: coef does not hold as many elements as pix")
+    scale, shift = _pix_affine(pix.dtype)
+    check(lib().lfvdm_wavelet_encode(ptr(pix, pix.dtype), _PIX[pix.dtype], scale, shift, ptr(coef), ptr(mean), ptr(rstd), N, Cc, H,
+                                     W, int(levels), WAVELET_NORMS[norm], stream()), "lfvdm_wavelet_encode")
+
+
+def wavelet_decode(coef, pix, levels, norm, mean=None, std=None):
+    """coef (N, 4^L C, H / 2^L, W / 2^L) float32 -> pix (N, C, H, W) float32, or uint8 ROUNDED to nearest
+    (lfvdm_wavelet_decode)."""
+    N, Cc, H, W = pix.shape
+    if coef.numel() != pix.numel() or pix.dtype not in _PIX:
+        raise RuntimeError("wavelet_decode: pix must be float32 or uint8 with as many elements as coef")
+    check(lib().lfvdm_wavelet_decode(ptr(coef), ptr(mean), ptr(std), ptr(pix, pix.dtype), _PIX[pix.dtype], N, Cc, H, W, int(levels),
+                                     WAVELET_NORMS[norm], stream()), "lfvdm_wavelet_decode")
+
+
+def prepare_batch_wavelet(pool, table, batch, frame_indices, obs_mask, latent_mask, levels, norm, mean=None, rstd=None):
+    """``prepare_batch`` on a pool of PIXELS (B, Tp, C, H, W), float32 or uint8, with the wavelet encode folded into the
+    gather: batch (B, F, 4^L C, H / 2^L, W / 2^L) (lfvdm_prepare_batch_wavelet)."""
+    B, Tp, Cc, H, W = pool.shape
+    F = table.shape[1]
+    if batch.numel() != B * F * Cc * H * W:
+        raise RuntimeError("prepare_batch_wavelet: batch does not hold B * F frames of the pool's size")
+    scale, shift = _pix_affine(pool.dtype)
+    check(lib().lfvdm_prepare_batch_wavelet(ptr(pool, pool.dtype), _PIX[pool.dtype], scale, shift, ptr(table, torch.int32), ptr(batch),
+                                            ptr(frame_indices, torch.int64), ptr(obs_mask), ptr(latent_mask), ptr(mean), ptr(rstd),
+                                            B, F, Tp, Cc, H, W, int(levels), WAVELET_NORMS[norm], stream()),
+          "lfvdm_prepare_batch_wavelet")
 
 
 def masked_mse(a, b, mask, out, B, T, frame_inner):

@@ -174,6 +174,9 @@ class GaussianDiffusion:
         self.diffusion_space = diffusion_space_kwargs.get("diffusion_space")
         self.pre_encoded = diffusion_space_kwargs.get("pre_encoded")
         self.pre_encoded_stats_dict = diffusion_space_kwargs.get("pre_encoded_stats_dict")
+        self.wavelet_levels = diffusion_space_kwargs.get("wavelet_levels", 1)
+        self.wavelet_norm = diffusion_space_kwargs.get("wavelet_norm", "range")
+        self.wavelet_stats = diffusion_space_kwargs.get("wavelet_stats")
         if self.pre_encoded:
             self.pre_encoded_stats_dict["mean"] = self.pre_encoded_stats_dict["mean"].reshape(1, 1, -1, 1, 1)
             self.pre_encoded_stats_dict["std"] = self.pre_encoded_stats_dict["std"].reshape(1, 1, -1, 1, 1)
@@ -1093,7 +1096,10 @@ class GaussianDiffusion:
         if self.diffusion_space in (None, "pixel"):
             return
         if self.diffusion_space == "wavelet":
-            raise NotImplementedError
+            # a Haar transform (improved_diffusion/wavelet.py): no weights, nothing to set up but the settings' validity
+            from . import wavelet
+            wavelet._check(self.wavelet_levels, self.wavelet_norm)
+            return
         if self.diffusion_space != "latent":
             raise ValueError(f"Unknown diffusion space: {self.diffusion_space}")
         import os
@@ -1122,9 +1128,13 @@ class GaussianDiffusion:
     @th.no_grad()
     def encode(self, video, chunk_size=10):
         """Pixels (B, T, 3, H, W) in [-1, 1] -> latents; identity in pixel space and for pre-encoded data
-        (reference :914-932)."""
+        (reference :914-932).  Wavelet space: the Haar coefficients of ``wavelet.wavelet_encode`` (float pixels in
+        [-1, 1] or uint8 frames; ``chunk_size`` is ignored)."""
         if self.diffusion_space in (None, "pixel") or self.pre_encoded:
             return video
+        if self.diffusion_space == "wavelet":
+            from . import wavelet
+            return wavelet.wavelet_encode(video, self.wavelet_levels, self.wavelet_norm, self.wavelet_stats)
         if self.vae is None:
             raise NotImplementedError("VAE encoding needs the stabilityai/stable-video-diffusion-img2vid weights: attach "
                                       "them with set_vae() / LFVDM_VAE_PATH, or pre-encode the dataset as the reference's "
@@ -1148,17 +1158,23 @@ class GaussianDiffusion:
         return video * st["std"].to(video.device, video.dtype) + st["mean"].to(video.device, video.dtype)
 
     def can_decode(self):
-        """Will ``decode`` return PIXELS?  (pixel space, or a latent space with its autoencoder attached)"""
-        return self.diffusion_space in (None, "pixel") or self.vae is not None
+        """Will ``decode`` return PIXELS?  (pixel or wavelet space, or a latent space with its autoencoder attached)"""
+        return self.diffusion_space in (None, "pixel", "wavelet") or self.vae is not None
 
     @th.no_grad()
     def decode(self, video, chunk_size=20, allow_latents=False):
         """Latents -> pixels (reference :934-947).  The reference always returns decoded pixels here, so without an
         attached VAE this RAISES: a caller that treats the result as video (evaluation, FVD) must never be handed
         4-channel latents silently.  ``allow_latents=True`` is the explicit opt-in for pre-encoded data: the
-        de-normalised latents ``z * std + mean`` - what the decoder would be fed - come back instead."""
+        de-normalised latents ``z * std + mean`` - what the decoder would be fed - come back instead.
+        Wavelet space always returns pixels (``wavelet.wavelet_decode``, float32 in [-1, 1]; ``chunk_size`` is ignored).
+        With ``wavelet_stats`` attached the coefficients are standardised, so ``clip_denoised=True`` is no longer a
+        valid bound for the sampling loops in that space."""
         if self.diffusion_space in (None, "pixel"):
             return video
+        if self.diffusion_space == "wavelet":
+            from . import wavelet
+            return wavelet.wavelet_decode(video, self.wavelet_levels, self.wavelet_norm, self.wavelet_stats)
         if self.pre_encoded:
             video = self.denormalize_latents(video)
         if self.vae is None:

@@ -378,14 +378,37 @@ class TrainLoop:
 
     def _micro_step_from_pool(self, pool, table, t, weights):
         """Device-side batch preparation + micro-step: gather the frames named by the index table and write the mask /
-        index tensors (lfvdm_prepare_batch), then the usual micro-step.  One capturable body."""
+        index tensors (lfvdm_prepare_batch), then the usual micro-step.  One capturable body.  Wavelet space: the pool
+        holds pixels and the gather writes their Haar coefficients (lfvdm_prepare_batch_wavelet)."""
         B, F = table.shape[0], table.shape[1]
-        micro = th.empty((B, F) + tuple(pool.shape[2:]), device=pool.device, dtype=th.float32)
         frame_indices = th.empty(B, F, device=pool.device, dtype=th.int64)
         obs_mask = th.empty(B, F, 1, 1, 1, device=pool.device, dtype=th.float32)
         latent_mask = th.empty_like(obs_mask)
-        nat.prepare_batch(pool, table, micro, frame_indices, obs_mask, latent_mask)
+        if self._wavelet_prep():
+            d = self.diffusion
+            m = 1 << d.wavelet_levels
+            C, H, W = pool.shape[2:]
+            micro = th.empty(B, F, m * m * C, H // m, W // m, device=pool.device, dtype=th.float32)
+            mean, rstd = self._wavelet_dev_stats(pool.device, m * m * C)
+            nat.prepare_batch_wavelet(pool, table, micro, frame_indices, obs_mask, latent_mask, d.wavelet_levels, d.wavelet_norm,
+                                      mean, rstd)
+        else:
+            micro = th.empty((B, F) + tuple(pool.shape[2:]), device=pool.device, dtype=th.float32)
+            nat.prepare_batch(pool, table, micro, frame_indices, obs_mask, latent_mask)
         return self._micro_step(micro, frame_indices, obs_mask, latent_mask, t, weights)
+
+    def _wavelet_dev_stats(self, device, channels):
+        """(mean, 1 / std) of ``wavelet_stats`` on the device, or (None, None); uploaded once, during the eager warm-up
+        steps (a captured step must not copy from the host)."""
+        st = getattr(self.diffusion, "wavelet_stats", None)
+        if st is None:
+            return None, None
+        cached = self.__dict__.get("_wavelet_stats_dev")
+        if cached is None or cached[0].device != device:
+            from . import wavelet
+            mean, std = wavelet._stats(st, channels, "cpu", th.float32)
+            cached = self._wavelet_stats_dev = (mean.to(device), wavelet._rstd(std).to(device))
+        return cached
 
     def _graphed_micro_step(self, inputs, body=None, upload=None):
         """Replay the captured micro-step (forward + backward, ~1000 launches) as ONE hipGraph: the training
@@ -438,12 +461,23 @@ class TrainLoop:
 
     def _device_prep_ok(self, batch1):
         """Device-side batch preparation applies to fixed-size batches of host tensors whose encode step is the identity
-        (pixel space or pre-encoded latents); LFVDM_DEVICE_BATCH_PREP=0 restores the host gather."""
+        (pixel space or pre-encoded latents), or the Haar transform of the wavelet space, which the gather kernel applies on
+        the way (float32 or uint8 frames); LFVDM_DEVICE_BATCH_PREP=0 restores the host gather."""
         d = self.diffusion
-        return (self.pad_with_random_frames and not batch1.is_cuda and dist_util.dev().type == "cuda"
-                and batch1.dtype == th.float32 and batch1[0, 0].numel() % 4 == 0
-                and (getattr(d, "diffusion_space", None) in (None, "pixel") or bool(getattr(d, "pre_encoded", False)))
-                and os.environ.get("LFVDM_DEVICE_BATCH_PREP", "1") != "0")
+        if not (self.pad_with_random_frames and not batch1.is_cuda and dist_util.dev().type == "cuda"
+                and os.environ.get("LFVDM_DEVICE_BATCH_PREP", "1") != "0"):
+            return False
+        if self._wavelet_prep():
+            m = 1 << d.wavelet_levels
+            return (batch1.dtype in (th.float32, th.uint8) and batch1.dim() == 5 and batch1.shape[-2] % m == 0
+                    and batch1.shape[-1] % m == 0)
+        return (batch1.dtype == th.float32 and batch1[0, 0].numel() % 4 == 0
+                and (getattr(d, "diffusion_space", None) in (None, "pixel") or bool(getattr(d, "pre_encoded", False))))
+
+    def _wavelet_prep(self):
+        """Does the device batch preparation have to encode (wavelet space on pixel data)?"""
+        d = self.diffusion
+        return getattr(d, "diffusion_space", None) == "wavelet" and not bool(getattr(d, "pre_encoded", False))
 
     # videos up to this many bytes travel whole and are gathered on the device; longer ones (CARLA: 1000 frames) are
     # thinned on the host to the frames the table names, so that only those cross PCIe
@@ -761,7 +795,7 @@ class TrainLoop:
                               'latent_mask': latent_mask.to(dev)},
                 latent_mask=latent_mask, return_attn_weights=False, return_decoded=False)
             samples = samples.cpu() * latent_mask + batch * obs_mask
-            renderable = self.diffusion.diffusion_space in (None, "pixel") or self.diffusion.vae is not None
+            renderable = self.diffusion.diffusion_space in (None, "pixel", "wavelet") or self.diffusion.vae is not None
             if renderable:     # latent space without an attached VAE: nothing to render, only the timing is logged
                 samples = self.decode(samples).float()
                 _mark_as_observed(samples[:, :n_obs])
