@@ -833,6 +833,29 @@ int lfvdm_prepare_batch_wavelet(const void* pool, int dtype, float scale, float 
                                 void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The "bouncing_shapes" procedural video dataset rendered on the device (csrc/shapes.hip, whose header comment is the
+ * definition: integer arithmetic only; improved_diffusion/shapes.py is the host reference and agrees bit for bit).
+ * lfvdm_shapes_trajectories: video_idx [n_videos] int64 (values below 2^32) -> traj [n_videos][T][n_shapes][2] int32 (x, y in
+ *   1/16 pixel) and consts [n_videos][n_shapes][4] int32 {kind 0 disc / 1 square, radius, r | g << 8 | b << 16, 0}.
+ *   split: 0 train, 1 test (disjoint Philox streams).  One thread per (video, shape), sequential over the T frames.
+ * lfvdm_shapes_render: out [B][F][3][H][W] of `dtype` LFVDM_PIX_U8, or LFVDM_PIX_F32 = lut[u8] (lut: 256 floats, required
+ *   for F32 only).  Batch element b owns Tp rows: row r is frame r % T of trajectory video b * (Tp / T) + r / T, Tp = T or 2 T.
+ *   table == NULL (whole videos): slot f shows row f, F <= Tp.  table [B][F][4] int32 (lfvdm_prepare_batch's, with Tp = 2 T the
+ *   rows of the pool [video 1 | padding video]): slot f shows row table[b][f][0], clamped into [0, Tp) as there, and
+ *   frame_indices / obs_mask / latent_mask - all three or none - are written as lfvdm_prepare_batch writes them.
+ * Both capturable; no atomics.  A NULL required pointer, H or W outside [8, 256] or not a multiple of 4, n_shapes outside
+ * [1, 4], T outside [1, 1024], B > 65535, a misaligned output (16 bytes for F32, 4 for U8; traj 8) -> LFVDM_E_SHAPE; an
+ * unknown dtype -> LFVDM_E_UNSUPPORTED; nothing is launched and no pointer is read in either case.
+ * Python side (video_datasets.py, --dataset bouncing_shapes), environment: LFVDM_SHAPES_N (n_shapes, 2), LFVDM_SHAPES_STOCHASTIC
+ * (1), LFVDM_SHAPES_SEED (0), LFVDM_SHAPES_SIZE ("64" or "HxW").
+ * ------------------------------------------------------------------------------------- */
+int lfvdm_shapes_trajectories(const int64_t* video_idx, int32_t* traj, int32_t* consts, uint64_t seed, int split, int n_videos,
+                              int T, int n_shapes, int H, int W, int stochastic, void* stream);
+int lfvdm_shapes_render(const int32_t* traj, const int32_t* consts, const int32_t* table, const float* lut, void* out, int dtype,
+                        int64_t* frame_indices, float* obs_mask, float* latent_mask, int B, int F, int Tp, int T, int n_shapes,
+                        int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Search for optimised conditioning frames (improved_diffusion/optimal_schedule.py; not in the reference).  One pass scores
  * G candidate conditioning sets on V videos as W = G * V windows of K slots; window w shows video w % V.
  *   table [W][K] int32   the video frame a slot shows, -1: padding        role [W][K] int32   LFVDM_SLOT_*

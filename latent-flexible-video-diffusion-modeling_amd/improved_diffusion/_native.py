@@ -198,6 +198,8 @@ _SIGS = {
     "lfvdm_wavelet_encode": ([c_fp, c_i, C.c_float, C.c_float, c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp], c_i),
     "lfvdm_wavelet_decode": ([c_fp, c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp], c_i),
     "lfvdm_prepare_batch_wavelet": ([c_fp, c_i, C.c_float, C.c_float] + [c_fp] * 7 + [c_i] * 8 + [c_fp], c_i),
+    "lfvdm_shapes_trajectories": ([c_fp, c_fp, c_fp, C.c_uint64] + [c_i] * 7 + [c_fp], c_i),
+    "lfvdm_shapes_render": ([c_fp] * 5 + [c_i] + [c_fp] * 3 + [c_i] * 7 + [c_fp], c_i),
     "lfvdm_search_assemble": ([c_fp] * 9 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_search_noise_qsample": ([c_fp] * 10 + [c_i] * 4 + [c_fp], c_i),
     "lfvdm_search_noise_fill": ([c_fp, C.c_uint64, c_i, c_i, c_fp] + [c_i] * 4 + [c_fp], c_i),
@@ -840,6 +842,38 @@ def prepare_batch_wavelet(pool, table, batch, frame_indices, obs_mask, latent_ma
                                             ptr(frame_indices, torch.int64), ptr(obs_mask), ptr(latent_mask), ptr(mean), ptr(rstd),
                                             B, F, Tp, Cc, H, W, int(levels), WAVELET_NORMS[norm], stream()),
           "lfvdm_prepare_batch_wavelet")
+
+
+def shapes_trajectories(video_idx, traj, consts, seed, split, stochastic, H, W):
+    """video_idx (N,) int64 -> traj (N, T, S, 2) int32 and consts (N, S, 4) int32 of the bouncing-shapes dataset
+    (lfvdm_shapes_trajectories); split: 0 train, 1 test."""
+    N, T, S = traj.shape[:3]
+    if video_idx.numel() != N or tuple(traj.shape) != (N, T, S, 2) or tuple(consts.shape) != (N, S, 4):
+        raise RuntimeError("shapes_trajectories: expected video_idx (N,), traj (N, T, S, 2), consts (N, S, 4)")
+    check(lib().lfvdm_shapes_trajectories(ptr(video_idx, torch.int64), ptr(traj, torch.int32), ptr(consts, torch.int32),
+                                          int(seed) % (1 << 64), int(split), N, T, S, int(H), int(W), int(bool(stochastic)),
+                                          stream()), "lfvdm_shapes_trajectories")
+
+
+def shapes_render(traj, consts, out, table=None, lut=None, frame_indices=None, obs_mask=None, latent_mask=None):
+    """traj (N, T, S, 2), consts (N, S, 4) -> out (B, F, 3, H, W) float32 (``lut``: 256 floats) or uint8; N = B (whole videos or
+    a table over one video) or 2 B (videos 2 b and 2 b + 1: video 1 and the padding video of batch element b).  ``table``
+    (B, F, 4) int32 names the frames as for ``prepare_batch`` and the three index / mask tensors are written when given
+    (lfvdm_shapes_render)."""
+    N, T, S = traj.shape[:3]
+    B, F, Cc, H, W = out.shape
+    if Cc != 3 or N % B or N // B not in (1, 2) or tuple(consts.shape) != (N, S, 4) or out.dtype not in _PIX:
+        raise RuntimeError("shapes_render: out (B, F, 3, H, W) float32 / uint8 over B or 2 B trajectory videos")
+    if table is not None and tuple(table.shape) != (B, F, 4):
+        raise RuntimeError("shapes_render: table must be (B, F, 4)")
+    for m in (frame_indices, obs_mask, latent_mask):
+        if m is not None and m.numel() != B * F:
+            raise RuntimeError("shapes_render: index / mask tensors hold B * F elements")
+    if lut is not None and lut.numel() != 256:
+        raise RuntimeError("shapes_render: the uint8 -> float table has 256 entries")
+    check(lib().lfvdm_shapes_render(ptr(traj, torch.int32), ptr(consts, torch.int32), ptr(table, torch.int32), ptr(lut),
+                                    ptr(out, out.dtype), _PIX[out.dtype], ptr(frame_indices, torch.int64), ptr(obs_mask),
+                                    ptr(latent_mask), B, F, (N // B) * T, T, S, H, W, stream()), "lfvdm_shapes_render")
 
 
 def masked_mse(a, b, mask, out, B, T, frame_inner):

@@ -498,8 +498,67 @@ class TrainLoop:
         table[:, :, 0] = np.arange(table.shape[1], dtype=np.int32)[None]
         return pool, table
 
+    # ------------------------------------------------------------------ batches rendered on the device (bouncing_shapes)
+    def _device_source(self):
+        """The device source of ``self.data`` (``shapes.ShapesBatches.device_source``) if this loop can render its batches
+        instead of loading them: fixed-size batches on a GPU, pixel space or the wavelet space on pixels;
+        LFVDM_DEVICE_BATCH_PREP=0 takes the host batches like any other iterator's."""
+        src = getattr(self.data, "device_source", None)
+        if src is None or not (self.pad_with_random_frames and dist_util.dev().type == "cuda"
+                               and os.environ.get("LFVDM_DEVICE_BATCH_PREP", "1") != "0"):
+            return None
+        d, p = self.diffusion, src.dataset.params
+        if self._wavelet_prep():
+            m = 1 << d.wavelet_levels
+            return src if p.H % m == 0 and p.W % m == 0 else None
+        pixel = getattr(d, "diffusion_space", None) in (None, "pixel") and not bool(getattr(d, "pre_encoded", False))
+        return src if pixel else None
+
+    def _micro_step_rendered(self, video_idx, table, t, weights):
+        """Render the frames the index table names straight into the micro-batch, with its index / mask tensors
+        (lfvdm_shapes_trajectories, lfvdm_shapes_render), then the usual micro-step.  One capturable body."""
+        micro, frame_indices, obs_mask, latent_mask = self._render_source.render_table(video_idx, table)
+        return self._micro_step(micro, frame_indices, obs_mask, latent_mask, t, weights)
+
+    def _micro_step_rendered_wavelet(self, video_idx, table, pool_table, t, weights):
+        """Wavelet space: render the named frames as a uint8 pool (slot f = row f, as the thinned pool of ``_pool_and_table``)
+        and let the existing gather encode it (lfvdm_prepare_batch_wavelet with the renumbered table)."""
+        pool = self._render_source.render_table(video_idx, table, dtype=th.uint8, masks=False)[0]
+        return self._micro_step_from_pool(pool, pool_table, t, weights)
+
+    def _forward_backward_rendered(self, src):
+        """``forward_backward`` for a data iterator with a device source: the host draws what it draws on the host path, in
+        the same order - the items of the two batches, then per micro-batch the index table and the timesteps - and uploads
+        only those; the frames are rendered inside the (captured) micro-step."""
+        items1, items2 = src.next_indices().numpy(), src.next_indices().numpy()
+        ds = src.dataset
+        src.lut(dist_util.dev())               # uploaded here, never inside a captured body
+        self._render_source = src
+        for i in range(0, len(items1), self.microbatch):
+            m1, m2 = items1[i:i + self.microbatch], items2[i:i + self.microbatch]
+            table = self.sample_index_table(len(m1), ds.T)
+            video_idx = th.from_numpy(np.stack([ds.video_indices(m1), ds.video_indices(m2)], axis=1))
+            t, weights = self.schedule_sampler.sample(len(m1), th.device("cpu"))
+            host, body = [video_idx, th.from_numpy(table)], self._micro_step_rendered
+            if self._wavelet_prep():
+                pool_table = table.copy()
+                pool_table[:, :, 0] = np.arange(table.shape[1], dtype=np.int32)[None]
+                host.append(th.from_numpy(pool_table))
+                body = self._micro_step_rendered_wavelet
+            upload = self._stage(*host, t, weights)
+            weighted, raw = self._graphed_micro_step(None, body=body, upload=upload)
+            t = self._dev_inputs[-2]           # the timesteps as the device saw them (loss-quartile logging)
+            self.exchange.micro_step_done()
+            if isinstance(self.schedule_sampler, LossAwareSampler):
+                self.schedule_sampler.update_with_local_losses(t, raw)
+            self._flush_loss_log()
+            self._stash_loss_log(t, weighted)
+
     def forward_backward(self):
         self.arena.zero_grad()
+        src = self._device_source()
+        if src is not None:
+            return self._forward_backward_rendered(src)
         batch1 = next(self.data)[0]
         batch2 = next(self.data)[0] if self.pad_with_random_frames else None
         for i in range(0, batch1.shape[0], self.microbatch):

@@ -37,6 +37,7 @@ default_T_dict = {
     "carla_no_traffic_2x_encoded": 1000,
     "synthetic_latent": 40,
     "synthetic_pixel": 40,
+    "bouncing_shapes": 100,
 }
 
 default_image_size_dict = {
@@ -47,6 +48,7 @@ default_image_size_dict = {
     "carla_no_traffic_2x_encoded": 32,
     "synthetic_latent": 16,
     "synthetic_pixel": 128,
+    "bouncing_shapes": 64,
 }
 
 data_encoding_stats_dict = {
@@ -171,6 +173,9 @@ def _open(dataset_name, T, split, shard, num_shards):
     T = default_T_dict[dataset_name] if T is None else T
     if dataset_name.startswith("synthetic"):
         return SyntheticVideoDataset(dataset_name, T=T, seed=1234 + shard + (0 if split == "train" else 10_000))
+    if dataset_name == "bouncing_shapes":
+        from . import shapes          # (shapes imports this module)
+        return shapes.open_dataset(T, split, shard, num_shards, default_image_size_dict[dataset_name])
     if dataset_name not in _FORMATS:
         raise Exception("no dataset", dataset_name)
     return VideoFiles(_FORMATS[dataset_name], split, T, shard, num_shards)
@@ -178,7 +183,16 @@ def _open(dataset_name, T, split, shard, num_shards):
 
 def load_data(dataset_name, batch_size, T=None, deterministic=False, num_workers=1, return_dataset=False):
     """Endless stream of training batches ``(video (B, T, C, H, W), {})`` from this rank's shard of the train split.
-    (``return_dataset=True`` makes the generator yield the Dataset once; ``get_train_dataset`` returns it directly.)"""
+    (``return_dataset=True`` makes the generator yield the Dataset once; ``get_train_dataset`` returns it directly.)
+    ``bouncing_shapes``: the iterator is a ``shapes.ShapesBatches`` - the same host batches, rendered in this process
+    (``num_workers`` is not used), plus ``device_source``, through which ``TrainLoop`` renders them on the device instead."""
+    if dataset_name == "bouncing_shapes" and not return_dataset:
+        from . import shapes
+        return shapes.ShapesBatches(get_train_dataset(dataset_name, T), batch_size, deterministic)
+    return _batches(dataset_name, batch_size, T, deterministic, num_workers, return_dataset)
+
+
+def _batches(dataset_name, batch_size, T, deterministic, num_workers, return_dataset):
     dataset = get_train_dataset(dataset_name, T)
     if return_dataset:
         yield dataset
