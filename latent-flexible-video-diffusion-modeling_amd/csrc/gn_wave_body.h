@@ -1,4 +1,4 @@
-// One-wave GroupNorm32(+FiLM)(+activation) of a (sample, 16 channels) slice (see norm_embed.hip, "gn_wave"), shared by
+// One-wave GroupNorm32(+FiLM)(+activation) of a (sample, 16 channels) slice (see groupnorm.hip, "gn_wave"), shared by
 // the per-launch kernel and the persistent level chain (level_chain.hip).
 #pragma once
 #include "common_hip.h"

@@ -1,7 +1,7 @@
 // GroupNorm(+FiLM)(+SiLU) backward for the fused "statistics -> affine in the conv operand" scheme, and the
 // temporal GroupNorm backward.  HBM/L2-bound reductions; wave = 64.
 //
-// Forward (norm_embed.hip):  z = x*A + B,  a = act(z),  A = rstd*g',  B = b' - mean*A,  g' = gamma*(1+scale).
+// Forward (groupnorm.hip):  z = x*A + B,  a = act(z),  A = rstd*g',  B = b' - mean*A,  g' = gamma*(1+scale).
 // Given da (gradient w.r.t. a, from the conv data gradient):
 //   dz      = da * act'(z)
 //   s1[n,c] = sum_p dz,          s2[n,c] = sum_p dz * xhat          (xhat = (x-mean)*rstd)
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(GB_THREADS) void gn_bwd_fused_kernel(
 // -------------------------------------------------------------------------------------
 // Large maps (pixel space, 32x32 latents, wide concats): the (sample, 8 groups) decomposition above gives N*4 workgroups
 // whatever P is - 80 workgroups streaming ~1 GB per GroupNorm at 20 x 128 x 128 x 128.  Chunked form, the decomposition
-// of the forward's gn_chunk_* kernels (norm_embed.hip): a workgroup owns a CHUNK of 8*PL positions of a (sample, 8 groups)
+// of the forward's gn_chunk_* kernels (groupnorm.hip): a workgroup owns a CHUNK of 8*PL positions of a (sample, 8 groups)
 // slice and keeps x and dz of the chunk in registers.
 //   pass 1 (gn_bwd_chunk_stats_kernel): per-channel partial sums s1, s2 of the chunk -> part[n][chunk][C][2]
 //   pass 2 (gn_bwd_chunk_apply_kernel): every workgroup sums the S partials of its channels IN CHUNK ORDER (its chunk's

@@ -441,26 +441,25 @@ class LinearFn(th.autograd.Function):
 def _gn_apply(a, b, C0, C1, N, P, gamma, beta, film, T, act):
     """GroupNorm(+FiLM)(+SiLU) applied once: -> (activated [N*P][C] tensor, coefA, coefB, stats).  The activated
     tensor feeds the implicit GEMM and (saved) the weight-gradient kernel as a raw operand (lfvdm_gn_apply)."""
-    C = C0 + C1
-    out = _new(N * P, C, like=a)
-    cA, cB, stats = _new(N, C, like=a), _new(N, C, like=a), _new(N, 32, 2, like=a)
-    L = nat.lib()
-    need = int(L.lfvdm_gn_apply_ws_floats(C, N, P))        # > 0: large map, chunked two-launch form
-    ws = _new(need, like=a) if need else None
-    nat.check(L.lfvdm_gn_apply_ws(
-        nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(gamma), nat.ptr(beta), film.data_ptr() if film is not None else None,
-        T if film is not None else 1, film.stride(0) if film is not None else 0, _EPS, act, nat.ptr(out), nat.ptr(cA),
-        nat.ptr(cB), nat.ptr(stats), nat.ptr(ws), need, nat.stream()), "lfvdm_gn_apply_ws")
-    return out, cA, cB, stats
+    out = _new(N * P, C0 + C1, like=a)
+    return (out,) + _gn_forward(a, b, C0, C1, N, P, gamma, beta, film, T, act, out)
 
 
-def _gn_forward(a, b, C0, C1, N, P, gamma, beta, film, T):
+def _gn_forward(a, b, C0, C1, N, P, gamma, beta, film, T, act=nat.ACT_NONE, out=None):
+    """-> (coefA, coefB, stats); with ``out`` also the activated tensor (on a large map by the chunked two-launch form)."""
     C = C0 + C1
     cA, cB, stats = _new(N, C, like=a), _new(N, C, like=a), _new(N, 32, 2, like=a)
-    nat.check(nat.lib().lfvdm_gn_coef_stats(
-        nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(gamma), nat.ptr(beta), film.data_ptr() if film is not None else None,
-        T if film is not None else 1, film.stride(0) if film is not None else 0, _EPS, nat.ptr(cA), nat.ptr(cB), nat.ptr(stats),
-        nat.stream()), "lfvdm_gn_coef_stats")
+    ws = []         # (the large map's workspace: alive until the launches are queued)
+
+    def alloc_ws(need):
+        ws.append(_new(need, like=a))
+        return nat.ptr(ws[0])
+
+    fkw = dict(film=film.data_ptr(), film_div=T, film_ld=film.stride(0)) if film is not None else {}
+    fn, args = nat.gn_fwd_call(alloc_ws, src0=nat.ptr(a), src1=nat.ptr(b), C0=C0, C1=C1, N=N, P=P, gamma=nat.ptr(gamma),
+                               beta=nat.ptr(beta), eps=_EPS, act=act, out=nat.ptr(out), coefA=nat.ptr(cA), coefB=nat.ptr(cB),
+                               stats=nat.ptr(stats), **fkw)
+    nat.check(fn(*args, nat.stream()), fn.__name__)
     return cA, cB, stats
 
 

@@ -73,12 +73,16 @@ def chain_stage(step, part_bases):
         return st
     g = st.gn
     if fn is L.lfvdm_gn_apply_part:
-        (g.src0, g.C0, g.N, g.P, g.cg, g.gamma, g.beta, g.eps, g.act, g.out, g.ldo) = args
-        g.film_div, (g.out_base, g.out_col) = 1, part_bases[args[9]]
-    elif fn is L.lfvdm_gn_apply and not any(args[14:]):           # (no coefA / coefB / statistics output)
-        (g.src0, g.src1, g.C0, g.C1, g.N, g.P, g.gamma, g.beta, g.film, g.film_div, g.film_ld, g.eps, g.act, g.out) = args[:14]
+        kw = dict(zip(nat.GN_APPLY_PART_ARGS, args), film_div=1)
+        g.out_base, g.out_col = part_bases[kw["out"]]
+    elif fn is L.lfvdm_gn_apply:
+        kw = dict(zip(nat.GN_APPLY_ARGS, args))
+        if any([kw.pop(k) for k in ("coefA", "coefB", "stats")]):      # (a stage writes the activated tensor only)
+            return None
     else:
         return None
+    for name, v in kw.items():
+        setattr(g, name, v)
     if g.N * g.P > CHAIN_MAX_M or L.lfvdm_chain_gn_ok(g.C0, g.C1, g.N, g.P) != 0:
         return None
     st.kind = nat.CHAIN_GN

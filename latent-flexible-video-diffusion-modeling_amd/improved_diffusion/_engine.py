@@ -148,16 +148,12 @@ class Plan:
 
     def gn_apply(self, a, b, C0, C1, N, P, gn, film, act, key):
         out = self.scratch(key, N * P, C0 + C1)
-        L = nat.lib()
-        args = (_p(a), _p(b) if b is not None else None, C0, C1, N, P, _p(gn.weight), _p(gn.bias),
-                _p(film) if film is not None else None, self.T if film is not None else 1,
-                self.rows_ld if film is not None else 0, gn.eps, act, _p(out), None, None, None)
-        need = int(L.lfvdm_gn_apply_ws_floats(C0 + C1, N, P))
-        if need:        # large map: chunk statistics + apply over thousands of workgroups (see lfvdm_gn_apply_ws)
-            ws = self.scratch("gn_ws", 1, need)
-            self.add(L.lfvdm_gn_apply_ws, *args, _p(ws), need)
-        else:
-            self.add(L.lfvdm_gn_apply, *args)
+        fkw = dict(film=_p(film), film_div=self.T, film_ld=self.rows_ld) if film is not None else {}
+        # (large map: chunk statistics + apply over thousands of workgroups, see lfvdm_gn_apply_ws)
+        fn, args = nat.gn_fwd_call(lambda need: _p(self.scratch("gn_ws", 1, need)), src0=_p(a), C0=C0, C1=C1, N=N, P=P,
+                                   src1=_p(b) if b is not None else None, gamma=_p(gn.weight), beta=_p(gn.bias), eps=gn.eps,
+                                   act=act, out=_p(out), **fkw)
+        self.add(fn, *args)
         return out
 
     def packed(self, weight, c0=0, c1=None):

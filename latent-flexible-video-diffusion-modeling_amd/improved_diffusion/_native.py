@@ -218,6 +218,27 @@ _SIGS = {
 
 EXPORTS = tuple(_SIGS)
 
+# Positional layouts (without the stream) of the spatial GroupNorm forward entries, by GnArgs field name where one exists.
+# The one place that knows the order: gn_fwd_call builds calls and plan steps from it, _chains.chain_stage reads plan
+# steps back by it, bench.py reads the same tuples by position.
+GN_APPLY_ARGS = ("src0", "src1", "C0", "C1", "N", "P", "gamma", "beta", "film", "film_div", "film_ld", "eps", "act", "out",
+                 "coefA", "coefB", "stats")                       # lfvdm_gn_apply; lfvdm_gn_apply_ws: + ("ws", "ws_floats")
+GN_APPLY_PART_ARGS = ("src0", "C0", "N", "P", "cg", "gamma", "beta", "eps", "act", "out", "ldo")      # lfvdm_gn_apply_part
+
+
+def gn_fwd_call(alloc_ws=None, **kw):
+    """-> (entry, its arguments without the stream) for keywords named as in GN_APPLY_ARGS (raw pointers or None; src1,
+    film and the three optional outputs default to absent).  No ``out``: lfvdm_gn_coef_stats, whose layout is the same
+    without act / out.  Otherwise lfvdm_gn_apply, or on a large map lfvdm_gn_apply_ws with ``alloc_ws(floats)`` -> pointer."""
+    L = lib()
+    kw = dict(dict(src1=None, C1=0, film=None, film_div=1, film_ld=0, act=ACT_NONE, out=None, coefA=None, coefB=None,
+                   stats=None), **kw)
+    if kw["out"] is None:
+        return L.lfvdm_gn_coef_stats, tuple(kw[k] for k in GN_APPLY_ARGS if k not in ("act", "out"))
+    args = tuple(kw[k] for k in GN_APPLY_ARGS)
+    need = int(L.lfvdm_gn_apply_ws_floats(kw["C0"] + kw["C1"], kw["N"], kw["P"]))
+    return (L.lfvdm_gn_apply_ws, args + (alloc_ws(need), need)) if need else (L.lfvdm_gn_apply, args)
+
 
 def lib():
     """Load (once) and return the shared library; raises if it has not been built."""

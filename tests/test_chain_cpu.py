@@ -382,3 +382,71 @@ def test_cfgB_plan_becomes_two_sample_local_chains_with_a_skip_side():
     # ... standing where their chains stood
     i = was_chain.index(True)
     assert all(s[0] is L.lfvdm_level_chain for s in pl2.steps[i:i + 8])
+
+
+def test_groupnorm_steps_keep_their_positional_layout():
+    """The (fn, args) tuples of the lfvdm_gn_apply / _ws / _part steps, position by position - what bench.py reads
+    (args[2:6] = C0, C1, N, P of an apply step, args[1:4] = C, N, P of a part step) and what chain_stage turns into
+    stages.  Two plans on CPU tensors (nothing is launched): the headline 16x16 one, and one on 64x64 maps whose
+    GroupNorms take the chunked two-launch form."""
+    import torch as th
+    sys.path.insert(0, ROOT)
+    import bench
+    from improved_diffusion import _engine as eng
+    model, _ = bench.make_model_and_diffusion(64, th.device("cpu"))
+    L = nat.lib()
+    norms = [m for m in model.modules() if hasattr(m, "num_groups")]
+
+    def norm_at(ptr):       # the GroupNorm whose weight holds this pointer, and the channel it points at
+        (m,) = [m for m in norms if 0 <= ptr - m.weight.data_ptr() < 4 * m.weight.numel()]
+        return m, (ptr - m.weight.data_ptr()) // 4
+
+    def check_plan(B, T, H, counts, **kw):
+        pl = eng.Plan(eng.Engine(model), B, T, H, H, False, **kw)
+        bufs = [t for t in pl.keep if isinstance(t, th.Tensor)]
+
+        def holds(ptr, floats):
+            return any(0 <= ptr - t.data_ptr() and ptr + 4 * floats <= t.data_ptr() + t.numel() * t.element_size() for t in bufs)
+
+        seen = {"lfvdm_gn_apply": 0, "lfvdm_gn_apply_ws": 0, "lfvdm_gn_apply_part": 0}
+        for fn, a in pl.steps:
+            if getattr(fn, "__name__", "") not in seen:
+                continue
+            seen[fn.__name__] += 1
+            assert fn is getattr(L, fn.__name__)
+            if fn is L.lfvdm_gn_apply_part:
+                gn, c0 = norm_at(a[5])
+                C, P, cg = gn.weight.numel() - c0, a[3], gn.weight.numel() // 32
+                assert a == (a[0], C, B * T, P, cg, gn.weight.data_ptr() + 4 * c0, gn.bias.data_ptr() + 4 * c0, gn.eps, nat.ACT_SILU,
+                             a[9], a[10])
+                assert c0 > 0 and a[10] in (C, C + c0) and P in (4, 16, 64, 256) and holds(a[0], B * T * P * C)
+                assert a[9] in pl.part_bases and holds(a[9], (B * T * P - 1) * a[10] + C)
+                continue
+            gn, c0 = norm_at(a[6])
+            C, P = gn.weight.numel(), a[5]
+            film = (a[8], T, pl.rows_ld) if a[8] is not None else (None, 1, 0)
+            want = (a[0], a[1], a[2], C - a[2], B * T, P, gn.weight.data_ptr(), gn.bias.data_ptr(), *film, gn.eps, a[12], a[13],
+                    None, None, None)
+            need = L.lfvdm_gn_apply_ws_floats(C, B * T, P)
+            if fn is L.lfvdm_gn_apply_ws:
+                assert need > 0 and a[18] == need and holds(a[17], need)
+                want += (a[17], need)
+            assert a == want and need == (0 if fn is L.lfvdm_gn_apply else a[18])
+            assert c0 == 0 and a[2] > 0 and (a[1] is None) == (a[3] == 0) and a[12] in (nat.ACT_NONE, nat.ACT_SILU)
+            assert P in (H * H, H * H // 4, H * H // 16, H * H // 64) and holds(a[0], B * T * P * a[2]) and holds(a[13], B * T * P * C)
+            assert a[8] is None or holds(a[8], (B - 1) * pl.rows_ld + 2 * C)
+        assert list(seen.values()) == counts
+        return pl
+
+    pl = check_plan(2, 20, 16, [8, 0, 4], time_steps=1000)
+    check_plan(1, 2, 64, [7, 18, 2])
+    # the stages of the chains carry the same values, field by field
+    assert pl.build_chains() == 2
+    stages = {id(step): st.gn for ch in pl.chains for step, st in ch["run"] if st.kind == nat.CHAIN_GN}
+    assert len(stages) == 4
+    for step in (s for ch in pl.chains for s in ch["steps"] if id(s) in stages):
+        a, g = step[1], stages[id(step)]
+        assert step[0] is L.lfvdm_gn_apply_part
+        assert (g.src0, g.C0, g.N, g.P, g.cg, g.gamma, g.beta, g.act, g.out, g.ldo) == a[:7] + a[8:] and abs(g.eps - a[7]) < 1e-12
+        assert (g.src1, g.C1, g.film, g.film_div, g.film_ld) == (None, 0, None, 1, 0)
+        assert (g.out_base, g.out_col) == pl.part_bases[a[9]]

@@ -637,7 +637,7 @@ def _check_coef(tag, c, cA, cB, N, P, act):
 
 @pytest.mark.parametrize("N,P,C0,C1,film,act,regime", GN_APPLY_CASES)
 def test_gn_apply_off_centre(nat, N, P, C0, C1, film, act, regime):
-    """lfvdm_gn_apply (gn_wave_body.h / norm_embed.hip): output, statistics and coefficients."""
+    """lfvdm_gn_apply (gn_wave_body.h / groupnorm.hip): output, statistics and coefficients."""
     c = gn_apply_case(N, P, C0, C1, film, act, regime)
     Cc, T = c["Cc"], c["T"]
     out = torch.full((N * P, Cc), float("nan"), device="cuda")
@@ -688,6 +688,35 @@ def test_gn_coef_off_centre(nat, N, P, C0, C1, film, act, regime):
     nat.gn_coef(g[0], g[1], C0, C1, N, P, g[2], g[3], g[4], T if film else 1, 2 * Cc if film else 0, EPS, cA, cB)
     pre = (c["x"].double().view(N, P, Cc) * cA.cpu().double()[:, None, :] + cB.cpu().double()[:, None, :]).reshape(N * P, Cc)
     held(f"gn_coef {N}x{P}x{C0}+{C1} {regime}", F.silu(pre) if act else pre, c["ref"], c["bud"]["bound"], c["bud"]["two"])
+
+
+# One shape per branch of gn_fwd_launch (csrc/groupnorm.hip): the one-wave kernel; its four-wave form (P >= 128, P % 64 == 0);
+# gn_coef_kernel<8> and <16> where gn_wave_launch refuses (P > 256; 32 channels per group, with P <= 8 resp. 16 float4
+# per thread: 4 pixel lanes at C = 1024); a concat with FiLM.
+GN_ENTRY_CASES = [(2, 16, 64, 0, False), (2, 128, 64, 0, False), (2, 260, 64, 0, False), (2, 520, 64, 0, False),
+                  (2, 16, 1024, 0, False), (2, 40, 1024, 0, False), (4, 16, 32, 32, True)]
+
+
+@pytest.mark.parametrize("N,P,C0,C1,film", GN_ENTRY_CASES)
+def test_gn_forward_entries_write_the_same_bits(nat, N, P, C0, C1, film):
+    """lfvdm_gn_coef, lfvdm_gn_coef_stats and lfvdm_gn_apply share one launch path and run the same kernel on the same input:
+    coefA / coefB of all three, and the statistics of the latter two, are bitwise equal (no tolerance)."""
+    Cc, T, L = C0 + C1, 2, nat.lib()
+    x = (rnd("gn_entries/x", N * P, Cc) + 0.5).cuda()
+    a, b = (x[:, :C0].contiguous(), x[:, C0:].contiguous()) if C1 else (x, None)
+    gamma, beta = (1.0 + rnd("gn_entries/gamma", Cc, scale=0.3)).cuda(), rnd("gn_entries/beta", Cc, scale=0.2).cuda()
+    fm = rnd("gn_entries/film", N // T, 2 * Cc, scale=0.3).cuda() if film else None
+    args = (nat.ptr(a), nat.ptr(b), C0, C1, N, P, nat.ptr(gamma), nat.ptr(beta), nat.ptr(fm), T if film else 1, 2 * Cc if film else 0, EPS)
+    got = [[torch.full(s, float("nan"), device="cuda") for s in ((N, Cc), (N, Cc), (N, 32, 2))] for _ in range(3)]
+    out = torch.full((N * P, Cc), float("nan"), device="cuda")
+    nat.check(L.lfvdm_gn_coef(*args, *map(nat.ptr, got[0][:2]), nat.stream()), "lfvdm_gn_coef")
+    nat.check(L.lfvdm_gn_coef_stats(*args, *map(nat.ptr, got[1]), nat.stream()), "lfvdm_gn_coef_stats")
+    nat.check(L.lfvdm_gn_apply(*args, nat.ACT_SILU, nat.ptr(out), *map(nat.ptr, got[2]), nat.stream()), "lfvdm_gn_apply")
+    bits = [[t.cpu().view(torch.int32) for t in g] for g in got]
+    assert all(bool(torch.isfinite(t).all()) for g in (got[0][:2], got[1], got[2], [out]) for t in g)
+    for k, name in enumerate(("coefA", "coefB")):
+        assert torch.equal(bits[0][k], bits[1][k]) and torch.equal(bits[1][k], bits[2][k]), name
+    assert torch.equal(bits[1][2], bits[2][2]), "stats"
 
 
 @pytest.mark.parametrize("B,T,P,Cc,regime", GNT_CASES, ids=[f"{b}-{t}-{p}-{c}-{_gnt_target(t, c)}-{r}" for b, t, p, c, r in GNT_CASES])

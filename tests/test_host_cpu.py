@@ -183,6 +183,64 @@ def test_gn_bwd_record_matches_its_binding_and_refuses_on_the_host():
     assert refused == dict.fromkeys(refused, 1), {k: v for k, v in refused.items() if v != 1}
 
 
+def test_gn_forward_refuses_on_the_host_and_its_name_tuples_match_the_bindings():
+    """The spatial GroupNorm forward entries refuse before a launch (gn_fwd_check in csrc/groupnorm.hip; lfvdm_gn_apply_part
+    by rules of its own), so the return codes are tabulated here without a device.  Every code is what the entries
+    returned before they shared one check (read from a build of that commit), except the cells in ``tightened``: calls
+    the old entries let through to a kernel that dereferences NULL.  _native's name tuples cover each binding's
+    arguments but the stream."""
+    from improved_diffusion import _native as nat
+    L = nat.lib()
+    ws_names = nat.GN_APPLY_ARGS + ("ws", "ws_floats")
+    coef_names = tuple(k for k in nat.GN_APPLY_ARGS if k not in ("act", "out"))
+    names = {"lfvdm_gn_coef_stats": coef_names, "lfvdm_gn_apply": nat.GN_APPLY_ARGS, "lfvdm_gn_apply_ws": ws_names,
+             "lfvdm_gn_apply_part": nat.GN_APPLY_PART_ARGS}
+    for entry, ks in names.items():
+        assert len(ks) == len(getattr(L, entry).argtypes) - 1 and len(set(ks)) == len(ks), entry
+    assert len(nat.GN_APPLY_ARGS) == 17 and len(nat.GN_APPLY_PART_ARGS) == 11
+
+    host = (ctypes.c_float * 4)()
+    p = ctypes.addressof(host)              # stands for a device pointer: a refused call reads none of them
+    base = dict(src0=p, src1=p, C0=64, C1=32, N=2, P=4, gamma=p, beta=p, film=None, film_div=1, film_ld=0, eps=1e-5, act=1,
+                out=p, coefA=p, coefB=p, stats=p, ws=None, ws_floats=0, cg=4, ldo=64)
+    chunked = 2 * 8 * (256 // (8 * 3 // 4)) + 1           # C = 96: the first P that takes the chunked pair
+    assert L.lfvdm_gn_apply_ws_floats(96, 2, chunked - 1) == 0
+    need = L.lfvdm_gn_apply_ws_floats(96, 2, chunked)
+    assert need == 2 * 32 * 3 * 2                         # (three chunks of 8 * 42 positions)
+
+    def rc(entry, **kw):
+        a = dict(base, **kw)
+        return getattr(L, entry)(*[a[k] for k in names[entry]], None)
+
+    got, tightened = {}, set()
+    for entry in ("lfvdm_gn_coef_stats", "lfvdm_gn_apply", "lfvdm_gn_apply_ws"):
+        cases = {"C = 0": dict(C0=0, C1=0), "C % 32": dict(C0=48, C1=0), "C > 1024": dict(C0=1024, C1=32), "C0 % 4": dict(C0=30, C1=2),
+                 "N = 0": dict(N=0), "P = 0": dict(P=0), "C1 > 0, no src1": dict(src1=None),
+                 "film, film_div = 0": dict(film=p, film_div=0, film_ld=192), "film, film_div < 0": dict(film=p, film_div=-1, film_ld=192),
+                 "coefA without coefB": dict(coefB=None), "coefB without coefA": dict(coefA=None),
+                 "no src0": dict(src0=None), "no gamma": dict(gamma=None), "no beta": dict(beta=None)}
+        if entry == "lfvdm_gn_coef_stats":
+            cases["no output at all"] = dict(coefA=None, coefB=None, stats=None)
+            tightened |= {(entry, k) for k in ("coefA without coefB", "coefB without coefA", "no output at all")}
+        else:
+            cases["no out"] = dict(out=None)
+        tightened |= {(entry, k) for k in ("no src0", "no gamma", "no beta")}
+        if entry == "lfvdm_gn_apply_ws":
+            cases.update({"chunked, ws = NULL": dict(P=chunked, ws=None, ws_floats=need),
+                          "chunked, short ws": dict(P=chunked, ws=p, ws_floats=need - 1),
+                          "chunked, N = 65536": dict(P=chunked, N=65536, ws=p, ws_floats=L.lfvdm_gn_apply_ws_floats(96, 65536, chunked))})
+        got.update({(entry, k): rc(entry, **kw) for k, kw in cases.items()})
+    part = {"cg = 3": dict(cg=3), "cg = 32": dict(cg=32), "cg = 0": dict(cg=0), "ldo < C": dict(ldo=60), "ldo % 4": dict(ldo=66),
+            "P > 256": dict(P=257), "P = 0": dict(P=0), "N = 0": dict(N=0), "N > 65535": dict(N=65536), "C % 16": dict(C0=72, ldo=72),
+            "C = 0": dict(C0=0), "no src": dict(src0=None), "no gamma": dict(gamma=None), "no beta": dict(beta=None), "no out": dict(out=None)}
+    got.update({("lfvdm_gn_apply_part", k): rc("lfvdm_gn_apply_part", **kw) for k, kw in part.items()})
+    E_SHAPE, E_UNSUPPORTED = 1, 3
+    want = dict.fromkeys(got, E_SHAPE)
+    want.update({("lfvdm_gn_apply_part", k): E_UNSUPPORTED for k in ("cg = 3", "cg = 32", "cg = 0")})
+    assert tightened <= set(got) and all(want[k] == E_SHAPE for k in tightened)
+    assert got == want, {k: v for k, v in got.items() if v != want[k]}
+
+
 def _loop_stub(max_frames=6, pad=True):
     from improved_diffusion.train_util import TrainLoop
     loop = TrainLoop.__new__(TrainLoop)
