@@ -27,6 +27,7 @@
 #ifndef LFVDM_HIP_H
 #define LFVDM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -643,6 +644,32 @@ int lfvdm_known_blend(float* x, const float* known, const float* mask, const flo
                       int HW, void* stream);
 int lfvdm_renoise(float* x, float* noise_out, const int64_t* t, const float* sqrt_1mbeta, const float* sqrt_beta,
                   const int64_t* seed, int B, int inner, void* stream);
+/* Dynamic thresholding of x0-hat (Saharia et al. 2022, Imagen section 2.3; not in the reference), four launches on `stream`
+ * (csrc/dyn_threshold.hip).  x / model_out / xhat are (B, T, frame_inner); per batch row b, t = t[b]:
+ *     p0    = model_out (LFVDM_MEAN_X0) | sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] model_out (LFVDM_MEAN_EPS), the latter in
+ *             the rounding of the update cell that will consume xhat: x0hat_fma == 0  fl(fl(r x) - fl(rm1 out)), the
+ *             pred_xstart of lfvdm_update_x0 / lfvdm_update_rng_x0 (clip = 0) under LFVDM_RULE_ANCESTRAL and the stochastic
+ *             LFVDM_RULE_DDIM; x0hat_fma != 0  fma(r, x, -fl(rm1 out)), that of the deterministic LFVDM_RULE_DDIM and of
+ *             lfvdm_update_ms_x0 - bit for bit in both cases
+ *     selected elements: those of the frames f with frame_mask[b][f] != 0 (frame_mask == NULL: all); n_sel their count
+ *     pos   = percentile (n_sel - 1) in double, k = floor(pos), frac = (float)(pos - k)
+ *     v_lo, v_hi = the order statistics of rank k and min(k + 1, n_sel - 1) of |p0| over the selected elements - exact
+ *     q     = v_lo + (v_hi - v_lo) frac in fp32 (torch.quantile's "linear"),  s = min(max(q, 1), max_value)
+ *     stats[b] = (v_lo, v_hi, s);  n_sel == 0: (0, 0, 1)
+ *     xhat  = fminf(fmaxf(p0, -s), s) / s (IEEE division) for EVERY element, selected or not
+ * xhat then enters any update entry above as the output of an x0-prediction model (LFVDM_MEAN_X0, clip = 0).  Every byte
+ * of xhat and stats is reproducible (integer atomics only).  max_value = +inf: no cap.  xhat may equal model_out.
+ * workspace: lfvdm_dyn_threshold_workspace(B, T * frame_inner) bytes, 16-byte aligned, zero-filled ONCE by the caller; a
+ * call returns it in the state the next call needs (no memset: the sequence is hipGraph-capturable, no host synchronisation,
+ * no allocation).  One workspace serves one stream at a time.  NaN inputs are outside the contract.
+ * A NULL required pointer (x and t included, whatever the mean type), an unknown mean_type, LFVDM_MEAN_EPS without its two
+ * tables, percentile outside (0, 1], max_value < 1 (or NaN), B outside [1, 65535] or T * frame_inner above 2^31 - 1 ->
+ * LFVDM_E_SHAPE, before anything is launched. */
+int lfvdm_dyn_threshold_workspace(int B, int64_t inner, size_t* bytes);
+int lfvdm_dyn_threshold(const float* x, const float* model_out, const int64_t* t, const float* sqrt_recip_acp,
+                        const float* sqrt_recipm1_acp, int mean_type, int x0hat_fma, const float* frame_mask, int B, int T,
+                        int64_t frame_inner, double percentile, float max_value, float* xhat, float* stats, void* workspace,
+                        void* stream);
 /* Sampler clock of the captured denoising step (the loop `for i in indices: t = th.tensor([i]*B)` of
  * gaussian_diffusion.py:509-512 and _WrappedModel's timestep map, respace.py:117-122, kept on the device):
  * t[b] <- max(t[b] - 1, 0);  model_t[b] <- model_timestep_table[t[b]]. */

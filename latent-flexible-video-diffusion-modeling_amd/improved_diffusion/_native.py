@@ -144,6 +144,8 @@ _SIGS = {
     "lfvdm_conv_out_update_ms_x0": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 2 + [c_i] * 6 + [c_fp], c_i),
     "lfvdm_known_blend": ([c_fp] * 9 + [c_i] * 4 + [c_fp], c_i),
     "lfvdm_renoise": ([c_fp] * 6 + [c_i, c_i, c_fp], c_i),
+    "lfvdm_dyn_threshold_workspace": ([c_i, C.c_int64, C.POINTER(C.c_size_t)], c_i),
+    "lfvdm_dyn_threshold": ([c_fp] * 5 + [c_i, c_i, c_fp, c_i, c_i, C.c_int64, C.c_double, C.c_float] + [c_fp] * 4, c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_vb_terms": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 4 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_vb_terms_bwd": ([c_fp] * 11 + [c_i, c_i, c_fp, c_i, c_i, c_i, c_fp], c_i),
@@ -769,6 +771,29 @@ def renoise(x, t, c, d, seed, noise_out=None):
     B = x.shape[0]
     check(lib().lfvdm_renoise(ptr(x), ptr(noise_out), ptr(t, torch.int64), ptr(c), ptr(d), ptr(seed, torch.int64), B,
                               x.numel() // B, stream()), "lfvdm_renoise")
+
+
+def dyn_threshold_workspace(B, inner):
+    """Bytes of workspace ``dyn_threshold`` needs for B rows of ``inner`` elements (lfvdm_dyn_threshold_workspace).  The
+    caller zero-fills it once; every call hands it back ready for the next."""
+    n = C.c_size_t(0)
+    check(lib().lfvdm_dyn_threshold_workspace(int(B), int(inner), C.byref(n)), "lfvdm_dyn_threshold_workspace")
+    return int(n.value)
+
+
+def dyn_threshold(x, out, t, recip, recipm1, mean_type, x0hat_fma, frame_mask, percentile, max_value, xhat, stats, workspace):
+    """Dynamic thresholding of x0-hat (lfvdm_dyn_threshold): x / out / xhat (B, T, ...), ``frame_mask`` (B, T) or None,
+    ``stats`` (B, 3) receives (v_lo, v_hi, s), ``max_value`` None: no cap.  ``x0hat_fma``: the rounding of an epsilon model's
+    x0-hat - that of the deterministic DDIM / multistep update (True) or of the ancestral / stochastic DDIM one (False).
+    ``xhat`` is then the ``out`` of an update entry under MEAN_X0 with clip off."""
+    B, T = x.shape[0], x.shape[1]
+    if out.shape != x.shape or xhat.shape != x.shape or stats.numel() != 3 * B or (
+            frame_mask is not None and frame_mask.numel() != B * T):
+        raise RuntimeError("dyn_threshold: out / xhat are shaped like x (B, T, ...), frame_mask is (B, T), stats is (B, 3)")
+    check(lib().lfvdm_dyn_threshold(ptr(x), ptr(out), ptr(t, torch.int64), ptr(recip), ptr(recipm1), int(mean_type),
+                                    int(bool(x0hat_fma)), ptr(frame_mask), B, T, x.numel() // (B * T), float(percentile),
+                                    float("inf") if max_value is None else float(max_value), ptr(xhat), ptr(stats),
+                                    ptr(workspace, torch.uint8), stream()), "lfvdm_dyn_threshold")
 
 
 def vb_terms(x_start, x_t, out, noise, t, recip, recipm1, c1, c2, post_logvar, model_logvar, mask, mean_type, clip, vb,

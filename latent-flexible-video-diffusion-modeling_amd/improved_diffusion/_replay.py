@@ -159,6 +159,19 @@ class GraphSampler(ReplayedStep):
         else:
             self.ddim = diffusion.ddim_tables(dev, self.rule[1]) if self.rule[0] == "ddim" else None
         self.update = diffusion._update_args(dev, self.rule)
+        # dynamic thresholding (GaussianDiffusion.set_dynamic_threshold), read ONCE here - it is part of the sampler cache
+        # keys: the threshold launches (lfvdm_dyn_threshold) follow the forward inside the captured step, over static
+        # buffers - x0-hat, (v_lo, v_hi, s) per sample, the workspace (zero-filled once) and the window's latent frames
+        # (B, T), which begin() uploads - and the update consumes ``xhat`` with the tuple of an x0-prediction model
+        self.threshold = diffusion._threshold(self.clip)
+        self.xhat = self.dyn_stats = self.dyn_ws = self.frame_mask = self.update_xhat = None
+        if self.threshold is not None:
+            B, T = self.shape[:2]
+            self.update_xhat = diffusion._update_args(dev, self.rule, as_xstart=True)
+            self.xhat = th.empty(self.shape, device=dev)
+            self.dyn_stats = th.zeros(B, 3, device=dev)
+            self.dyn_ws = th.zeros(nat.dyn_threshold_workspace(B, self.xhat[0].numel()), dtype=th.uint8, device=dev)
+            self.frame_mask = th.ones(B, T, device=dev)
         self.noise = th.empty(self.shape, device=dev)
         # the step's x0-hat; under the multistep rule also the history the next step reads (in and out of one launch)
         self.pred = th.empty(self.shape, device=dev)
@@ -218,7 +231,10 @@ class GraphSampler(ReplayedStep):
         in_kernel = det or (not self.inject_noise and os.environ.get("LFVDM_SAMPLER_NOISE", "kernel") != "torch")
         # the x_{t-1} update rides in the plan's last launch (output conv + update: lfvdm_conv_out_update_x0) where the
         # shape allows; LFVDM_FUSED_HEAD=0 keeps the two launches (A/B aid)
-        fused = (os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
+        # under dynamic thresholding the head conv is never fused with the update (the branch of LFVDM_FUSED_HEAD=0, whatever
+        # the environment says): the quantile needs the whole x0-hat before any element can be updated
+        dyn = self.threshold is not None
+        fused = (not dyn and os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
                  and pl.fuse_head_update(self.t_buf, self.tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
                                          ddim=self.ddim, predict_xstart=self.x0_mode))
         # device-side clock: t <- max(t - 1, 0), model timestep <- table[t]  (t_buf holds "previous t"); with timestep
@@ -231,20 +247,27 @@ class GraphSampler(ReplayedStep):
             pl.launch()
         draw = not (fused or in_kernel or self.inject_noise)
         # launches of a step beside the plan's own (bench.py reports launches per step): the clock, the update, the draw
-        self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw)
+        # (+ the four launches of the dynamic threshold)
+        self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw) + (4 if dyn else 0)
         if fused:
             return
+        out, clip = pl.out, self.clip
+        if dyn:      # x0-hat of this model's mean type -> xhat, thresholded; the update then sees an x0 model's output
+            nat.dyn_threshold(pl.x_in, pl.out, self.t_buf, recip, recipm1, mean_type, self.diffusion._x0hat_fma(self.update),
+                              self.frame_mask, self.threshold[0], self.threshold[1], self.xhat, self.dyn_stats, self.dyn_ws)
+            recip, recipm1, c1, c2, sg, rule, mean_type = self.update_xhat
+            out, clip = self.xhat, False
         if self.multistep:
-            nat.update_ms_x0(pl.x_in, pl.out, self.pred, self.t_buf, recip, recipm1, c1, c2, sg, mean_type, self.clip, pl.x_in,
+            nat.update_ms_x0(pl.x_in, out, self.pred, self.t_buf, recip, recipm1, c1, c2, sg, mean_type, clip, pl.x_in,
                              self.pred)
             return
         if in_kernel:
-            nat.update_rng_x0(pl.x_in, pl.out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
-                              mean_type, self.clip, pl.x_in, None if det else self.seed, self.pred)
+            nat.update_rng_x0(pl.x_in, out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
+                              mean_type, clip, pl.x_in, None if det else self.seed, self.pred)
             return
         if draw:
             self.noise.normal_()
-        nat.update_x0(pl.x_in, pl.out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, self.clip, pl.x_in,
+        nat.update_x0(pl.x_in, out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, clip, pl.x_in,
                       self.pred)
 
     def begin(self, img, model_kwargs, known=None, known_mask=None, known_eps=None):
@@ -260,6 +283,12 @@ class GraphSampler(ReplayedStep):
             self.known_mask.copy_(known_mask)
             if known_eps is not None:
                 self.known_eps.copy_(known_eps)
+        if self.frame_mask is not None:      # the window's latent frames steer the threshold; before the replay, never in it
+            lm = model_kwargs.get("latent_mask")
+            if lm is None:
+                self.frame_mask.fill_(1.0)
+            else:
+                self.frame_mask.copy_(lm.reshape(self.frame_mask.shape))
         self._begin_chain(img, model_kwargs)
         self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
         if self.multistep:

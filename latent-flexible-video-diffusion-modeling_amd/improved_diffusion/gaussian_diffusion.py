@@ -34,7 +34,12 @@ What is native here
     not in the reference): float64 tables from this diffusion's own ``alphas_cumprod``, and one HIP launch that reads target and
     output once and returns mse, eval-mse and loss = w[t] * mse with the weight gathered by ``t`` on the device
     (csrc/train_loss.hip, ``_autograd._TrainLoss``).  Off by default; its effect on this model's convergence or sample
-    quality has not been measured.
+    quality has not been measured;
+  * dynamic thresholding of x0-hat (``set_dynamic_threshold``; Saharia et al. 2022, Imagen section 2.3 - not in the
+    reference) in every sampler: four HIP launches (csrc/dyn_threshold.hip, an exact radix select of the per-sample
+    quantile of |x0-hat| over the window's latent frames) write the thresholded x0-hat, which the step's usual update
+    launch consumes as the output of an x0-prediction model; the replayed step keeps its graph, its in-kernel noise and the
+    known-region blend.  Off by default; its effect on sample quality has not been measured.
 
 Out of scope (not reached by the default CLIs): learned sigma (``learn_sigma=True``, also together with
 ``use_kl``: the reference's own 5-D code path asserts on it, so there is no behaviour to match),
@@ -141,6 +146,53 @@ def parse_loss_weighting(spec):
     return kw
 
 
+def parse_dynamic_threshold(spec):
+    """"0.995" or "0.995:1.5" (percentile[:max_value]) -> the keyword arguments of ``GaussianDiffusion.set_dynamic_threshold``
+    (what LFVDM_DYNAMIC_THRESHOLD holds); "" and "none": thresholding off.  Only the shape of the string is judged here - the
+    setter validates the values.  ValueError otherwise."""
+    if not isinstance(spec, str):
+        raise ValueError(f"dynamic threshold must be a string such as '0.995' or '0.995:1.5', got {spec!r}")
+    parts = [s.strip() for s in spec.strip().split(":")]
+    if parts in ([""], ["none"]):
+        return {"percentile": None, "max_value": None}
+    if len(parts) > 2:
+        raise ValueError(f"dynamic threshold {spec!r}: 'percentile' or 'percentile:max_value'")
+    try:
+        vals = [float(p) for p in parts]
+    except ValueError:
+        raise ValueError(f"dynamic threshold {spec!r}: percentile and max_value must be numbers") from None
+    return {"percentile": vals[0], "max_value": vals[1] if len(vals) == 2 else None}
+
+
+def dynamic_threshold_reference(pred_xstart, latent_mask, percentile, max_value, return_scale=False, dtype=th.float64):
+    """Dynamic thresholding of x0-hat (Saharia et al. 2022, Imagen section 2.3) in plain torch, float64 inside, on any device:
+    the semantics of lfvdm_dyn_threshold (include/lfvdm_hip.h) and the yardstick of its tests.  Per sample b of
+    ``pred_xstart`` (B, T, ...): over the elements of the frames with ``latent_mask[b, f] != 0`` (``latent_mask``: B * T values
+    or None = all frames), pos = percentile (n_sel - 1), k = floor(pos), v_lo / v_hi = the order statistics of rank k and
+    min(k + 1, n_sel - 1) of |x0-hat|, q = v_lo + (v_hi - v_lo) (pos - k) - ``torch.quantile``'s "linear" - and
+    s = min(max(q, 1), max_value); a sample without a selected element has s = 1.  Returns clamp(x0-hat, -s, s) / s for
+    every element in the dtype of ``pred_xstart``; ``return_scale``: also s, (B,).  ``dtype``: what "inside" is - float32
+    gives the tests their model of the kernel's own precision."""
+    B = pred_xstart.shape[0]
+    p = pred_xstart.to(dtype)
+    a = p.abs().reshape(B, pred_xstart.shape[1] if pred_xstart.dim() > 1 else 1, -1)
+    keep = None if latent_mask is None else latent_mask.reshape(B, a.shape[1]) != 0
+    s = th.ones(B, dtype=dtype, device=p.device)
+    for b in range(B):
+        v = (a[b] if keep is None else a[b][keep[b].to(a.device)]).reshape(-1)
+        n = v.numel()
+        if n == 0:
+            continue
+        v = v.sort().values
+        pos = float(percentile) * (n - 1)
+        k = min(int(math.floor(pos)), n - 1)
+        q = v[k] + (v[min(k + 1, n - 1)] - v[k]) * (pos - k)
+        s[b] = q.clamp(min=1.0) if max_value is None else q.clamp(min=1.0).clamp(max=float(max_value))
+    sb = _bshape(s, p.dim())
+    out = (th.minimum(th.maximum(p, -sb), sb) / sb).to(pred_xstart.dtype)
+    return (out, s) if return_scale else out
+
+
 class GaussianDiffusion:
     """Training / sampling utilities (reference :101-181).  Same constructor and attributes."""
 
@@ -187,6 +239,9 @@ class GaussianDiffusion:
         self._known_samplers = {}      # the known-region samplers: their step ends with one more launch (other graphs)
         self._bpd_evals = {}
         self.set_loss_weighting("none")
+        self._dyn_ws = {}              # (device, B) -> the eager steps' threshold workspace
+        self.last_threshold_stats = None
+        self.set_dynamic_threshold()
         self.setup_enc_dec()
 
     # ------------------------------------------------------------------ tables on device
@@ -395,6 +450,62 @@ class GaussianDiffusion:
             tb = self._loss_weight_cache[key] = th.from_numpy(self._loss_weights).float().to(device)
         return tb
 
+    # ------------------------------------------------------------------ dynamic thresholding of x0-hat (not in the reference)
+    def set_dynamic_threshold(self, percentile=None, max_value=None):
+        """Dynamic thresholding (Saharia et al. 2022, Imagen section 2.3) in every sampler of this diffusion: where
+        ``clip_denoised`` is true, x0-hat is not clamped to [-1, 1] but, per sample, to [-s, s] and divided by s, with s the
+        ``percentile`` quantile (0 < percentile <= 1) of |x0-hat| over the window's latent frames, raised to at least 1 and
+        capped at ``max_value`` (>= 1; None: no cap) - ``dynamic_threshold_reference``.  ``percentile=None`` (the default):
+        the static clamp, exactly the code path it always was.  With ``clip_denoised=False`` nothing changes either way.
+
+        Native: lfvdm_dyn_threshold writes the thresholded x0-hat, which the step's usual update launch then consumes as
+        the output of an x0-prediction model; the replayed step keeps its graph (the head conv is then not fused with the
+        update), its in-kernel noise and the known-region blend.  A ``denoised_fn`` is applied first, and that route
+        thresholds with the reference function.  Thresholding is a sampling device: the bits-per-dim evaluator and the
+        variational-bound terms keep the static clamp.  Its effect on the sample quality of a trained model has not been
+        measured.  ValueError: a percentile outside (0, 1], a max_value below 1, or a max_value without a percentile."""
+        def number(name, v):
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"dynamic threshold: {name} must be a number, got {v!r}") from None
+            return v
+        if percentile is None:
+            if max_value is not None:
+                raise ValueError("dynamic threshold: max_value needs a percentile")
+            self._dyn_threshold = None
+            return
+        p = number("percentile", percentile)
+        if not (0.0 < p <= 1.0):
+            raise ValueError(f"dynamic threshold: 0 < percentile <= 1, got {p!r}")
+        m = None
+        if max_value is not None:
+            m = number("max_value", max_value)
+            if not m >= 1.0:
+                raise ValueError(f"dynamic threshold: max_value >= 1, got {m!r}")
+            if math.isinf(m):
+                m = None
+        self._dyn_threshold = (p, m)
+
+    @property
+    def dynamic_threshold(self):
+        """(percentile, max_value or None) in force, or None: the static clamp."""
+        return self._dyn_threshold
+
+    def _threshold(self, clip_denoised):
+        """The setting a step with this ``clip_denoised`` runs under: (percentile, max_value) or None."""
+        return self._dyn_threshold if clip_denoised else None
+
+    @staticmethod
+    def _frame_mask(latent_mask, x):
+        """A window's ``latent_mask`` (B * T values in any shape, or None) as the (B, T) float tensor the kernel reads."""
+        if latent_mask is None:
+            return None
+        B, T = x.shape[0], x.shape[1]
+        if latent_mask.numel() != B * T:
+            raise ValueError(f"latent_mask holds one value per frame (B, T) = {(B, T)}, got {tuple(latent_mask.shape)}")
+        return latent_mask.to(device=x.device, dtype=th.float32).reshape(B, T).contiguous()
+
     def _gather(self, name, t, ndim):
         return _bshape(self.tables(t.device)[name][t], ndim)
 
@@ -462,24 +573,58 @@ class GaussianDiffusion:
         return self._predict_xstart_from_eps(x_t, t, model_output)
 
     # ------------------------------------------------------------------ p(x_{t-1} | x_t)
-    def _update_args(self, device, rule=("ancestral",), reverse=False):
+    def _update_args(self, device, rule=("ancestral",), reverse=False, as_xstart=False):
         """(recip, recipm1, c1, c2, sg, RULE_*, MEAN_*) of the update ``rule`` - ("ancestral",), ("ddim", eta) or
         ("dpmpp2m",), whose k3 rides in the ``sg`` place - of this model's mean type: what every update launch of the
-        package is issued with (``_engine.update_args``)."""
+        package is issued with (``_engine.update_args``).  ``as_xstart``: the tuple of an x0-prediction model whatever this
+        model's mean type - the same c1 / c2 / sg tables - for the update behind the dynamic threshold, whose input IS an
+        x0-hat."""
         from ._engine import update_args
         if rule[0] == "dpmpp2m":
             ddim = self.dpm_solver_tables(device)
         else:
             ddim = self.ddim_tables(device, rule[1], reverse) if rule[0] == "ddim" else None
-        return update_args(self.tables(device), ddim, self.predicts_xstart)
+        return update_args(self.tables(device), ddim, self.predicts_xstart or as_xstart)
+
+    @staticmethod
+    def _x0hat_fma(update):
+        """Which rounding of an epsilon model's x0-hat the update cell of this ``_update_args`` tuple has
+        (lfvdm_dyn_threshold's ``x0hat_fma``): the deterministic DDIM cell and the multistep entries evaluate one fma."""
+        _, _, _, _, sg, R, _ = update
+        return R == nat.RULE_DPMPP2M or (R == nat.RULE_DDIM and sg is None)
+
+    def _dyn_threshold_eager(self, x, out, t, update, thr, latent_mask):
+        """lfvdm_dyn_threshold for an eager step -> the thresholded x0-hat; (v_lo, v_hi, s) per sample stay in
+        ``last_threshold_stats``.  The workspace is kept per (device, batch size): zero-filled once."""
+        recip, recipm1, _, _, _, _, M = update
+        B = x.shape[0]
+        key = (str(x.device), B, x.numel() // B)
+        ws = self._dyn_ws.get(key)
+        if ws is None:
+            while len(self._dyn_ws) >= 4:
+                self._dyn_ws.pop(next(iter(self._dyn_ws)))
+            ws = self._dyn_ws[key] = th.zeros(nat.dyn_threshold_workspace(B, x.numel() // B), dtype=th.uint8, device=x.device)
+        xhat = th.empty_like(x, memory_format=th.contiguous_format)
+        stats = th.empty(B, 3, device=x.device)
+        nat.dyn_threshold(x.contiguous(), out.contiguous(), t.to(th.int64).contiguous(), recip, recipm1, M,
+                          self._x0hat_fma(update), self._frame_mask(latent_mask, x), thr[0], thr[1], xhat, stats, ws)
+        self.last_threshold_stats = stats
+        return xhat
 
     # ``out`` below is the network's output: the noise, or x0-hat when ``predicts_xstart``
-    def _update(self, x, out, t, noise, clip_denoised, rule=("ancestral",), reverse=False, want_mean=False, hist=None):
+    def _update(self, x, out, t, noise, clip_denoised, rule=("ancestral",), reverse=False, want_mean=False, hist=None,
+                latent_mask=None):
         """One fused launch (lfvdm_update_x0) -> sample, x0-hat, and the mean on request.  ``noise`` None: the noise-free
         call of ``p_mean_variance`` (the ancestral kernel wants a pointer: ``x`` stands in); a deterministic DDIM rule
         reads no noise at all.  The multistep rule (lfvdm_update_ms_x0) reads ``hist``, the x0-hat of the step before
-        (None: a first-order step), and no noise either."""
-        recip, recipm1, c1, c2, sg, R, M = self._update_args(x.device, rule, reverse)
+        (None: a first-order step), and no noise either.  Under ``set_dynamic_threshold`` (and ``clip_denoised``) the
+        threshold launches come first (``latent_mask``: the window's latent frames, None = all) and the same update then
+        runs on their result with the tuple of an x0-prediction model and the clamp off."""
+        thr = self._threshold(clip_denoised)
+        if thr is not None:
+            out = self._dyn_threshold_eager(x, out, t, self._update_args(x.device, rule, reverse), thr, latent_mask)
+            clip_denoised = False
+        recip, recipm1, c1, c2, sg, R, M = self._update_args(x.device, rule, reverse, as_xstart=thr is not None)
         sample = th.empty_like(x, memory_format=th.contiguous_format)
         pred = th.empty_like(sample)
         if R == nat.RULE_DPMPP2M:
@@ -492,14 +637,19 @@ class GaussianDiffusion:
                       clip_denoised, sample, pred, mean)
         return sample, pred, mean
 
-    def _update_denoised(self, x, out, t, noise, clip_denoised, denoised_fn, rule=("ancestral",), reverse=False, hist=None):
+    def _update_denoised(self, x, out, t, noise, clip_denoised, denoised_fn, rule=("ancestral",), reverse=False, hist=None,
+                         latent_mask=None):
         """The same update with a user function applied to x0-hat before clipping (reference process_xstart,
         :305-309).  ``denoised_fn`` is arbitrary Python on a tensor, so this rarely used variant is composed of
         elementwise device ops around it instead of the fused kernel:  c1[t] * p0 + c2[t] * x + [t != 0] * sigma[t] * z,
-        or, under the multistep rule, + k3[t] * (p0 - hist) in the noise's place."""
+        or, under the multistep rule, + k3[t] * (p0 - hist) in the noise's place.  Under ``set_dynamic_threshold`` the
+        clamp's place is taken by ``dynamic_threshold_reference`` over the frames of ``latent_mask``."""
         n = x.dim()
         pred = denoised_fn(self._xstart_from_output(x, t, out))
-        if clip_denoised:
+        thr = self._threshold(clip_denoised)
+        if thr is not None:
+            pred = dynamic_threshold_reference(pred, latent_mask, thr[0], thr[1])
+        elif clip_denoised:
             pred = pred.clamp(-1, 1)
         _, _, c1, c2, sg, R, _ = self._update_args(x.device, rule, reverse)
         mean = _bshape(c1[t], n) * pred + _bshape(c2[t], n) * x
@@ -523,9 +673,11 @@ class GaussianDiffusion:
         assert t.shape == (B,)
         eps, attn = model(x, self._scale_timesteps(t), return_attn_weights=return_attn_weights, **model_kwargs)
         if denoised_fn is not None:
-            _, pred, mean = self._update_denoised(x, eps, t, None, clip_denoised, denoised_fn)
+            _, pred, mean = self._update_denoised(x, eps, t, None, clip_denoised, denoised_fn,
+                                                  latent_mask=model_kwargs.get("latent_mask"))
         else:   # noise-free update: the kernel returns the posterior mean and x0-hat in one pass
-            _, pred, mean = self._update(x, eps, t, None, clip_denoised, want_mean=True)
+            _, pred, mean = self._update(x, eps, t, None, clip_denoised, want_mean=True,
+                                         latent_mask=model_kwargs.get("latent_mask"))
         n = x.dim()
         return {"mean": mean, "variance": self._gather("model_variance", t, n).expand(x.shape),
                 "log_variance": self._gather("model_log_variance", t, n).expand(x.shape),
@@ -541,9 +693,10 @@ class GaussianDiffusion:
         if noise is None:
             noise = th.randn_like(x)
         if denoised_fn is not None:
-            sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn)
+            sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn,
+                                                    latent_mask=model_kwargs.get("latent_mask"))
         else:
-            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised)
+            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised, latent_mask=model_kwargs.get("latent_mask"))
         return {"sample": sample, "pred_xstart": pred, "attn": attn}
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
@@ -731,9 +884,11 @@ class GaussianDiffusion:
         if float(eta) != 0.0 and noise is None:
             noise = th.randn_like(x)
         if denoised_fn is not None:
-            sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn, ("ddim", eta), reverse)
+            sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn, ("ddim", eta), reverse,
+                                                    latent_mask=model_kwargs.get("latent_mask"))
         else:
-            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised, ("ddim", eta), reverse)
+            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised, ("ddim", eta), reverse,
+                                           latent_mask=model_kwargs.get("latent_mask"))
         return {"sample": sample, "pred_xstart": pred}
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, noise=None):
@@ -775,9 +930,10 @@ class GaussianDiffusion:
         out, _ = model(x, self._scale_timesteps(t), return_attn_weights=False, **model_kwargs)
         if denoised_fn is not None:
             sample, pred, _ = self._update_denoised(x, out, t, None, clip_denoised, denoised_fn, ("dpmpp2m",),
-                                                    hist=prev_pred_xstart)
+                                                    hist=prev_pred_xstart, latent_mask=model_kwargs.get("latent_mask"))
         else:
-            sample, pred, _ = self._update(x, out, t, None, clip_denoised, ("dpmpp2m",), hist=prev_pred_xstart)
+            sample, pred, _ = self._update(x, out, t, None, clip_denoised, ("dpmpp2m",), hist=prev_pred_xstart,
+                                           latent_mask=model_kwargs.get("latent_mask"))
         return {"sample": sample, "pred_xstart": pred}
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
@@ -813,8 +969,9 @@ class GaussianDiffusion:
     def _graph_sampler(self, unet, shape, clip_denoised, rule=("ancestral",)):
         # the update rule is part of the key (appended: position 1 stays the shape): a DDIM chain and an ancestral chain on
         # the same shape never share a captured graph
-        return self._cached_sampler(self._samplers, (id(unet), shape, bool(clip_denoised), tuple(rule)), unet, shape,
-                                    clip_denoised, rule)
+        # and so is the dynamic threshold in force (last; None: the static clamp): the sampler reads it when it is built
+        key = (id(unet), shape, bool(clip_denoised), tuple(rule), self._threshold(clip_denoised))
+        return self._cached_sampler(self._samplers, key, unet, shape, clip_denoised, rule)
 
     # ------------------------------------------------------------------ known-region sampling (RePaint; not in the reference)
     _KNOWN_RULES = {"ancestral": lambda eta: ("ancestral",), "ddim": lambda eta: ("ddim", float(eta)),
@@ -833,8 +990,8 @@ class GaussianDiffusion:
     def _known_region_sampler(self, unet, shape, clip_denoised, rule, fixed_noise):
         """``_graph_sampler`` for samplers whose captured step ends with the blend launch.  They live in a cache of their
         own: the plain samplers, their graphs and their launch counts are what they were."""
-        return self._cached_sampler(self._known_samplers, (id(unet), shape, bool(clip_denoised), tuple(rule), "known"), unet,
-                                    shape, clip_denoised, rule, known_fixed=bool(fixed_noise))
+        key = (id(unet), shape, bool(clip_denoised), tuple(rule), "known", self._threshold(clip_denoised))
+        return self._cached_sampler(self._known_samplers, key, unet, shape, clip_denoised, rule, known_fixed=bool(fixed_noise))
 
     @staticmethod
     def _fork_generator(device):

@@ -39,7 +39,9 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     args needs: n_obs, max_frames, max_latent_frames, sampling_scheme, clip_denoised, device and optionally
     optimality / eval_dir (an ``optimal_schedule.pt`` under eval_dir), use_ddim / ddim_eta (DDIM instead of the ancestral
     chain; in the reference ``--use_ddim`` only renames the results folder, here it selects the sampler), use_dpm_solver
-    (DPM-Solver++(2M) instead; together with use_ddim: ValueError).  Returns ``(samples, indices_used)``
+    (DPM-Solver++(2M) instead; together with use_ddim: ValueError), dynamic_threshold / dynamic_threshold_max (a percentile
+    and an optional cap: ``diffusion.set_dynamic_threshold`` is called with them before the first window; without the
+    attribute, LFVDM_DYNAMIC_THRESHOLD="0.995" or "0.995:1.5" is read; neither: the diffusion's setting stays).  Returns ``(samples, indices_used)``
     with ``samples`` on batch's device and ``indices_used`` the list of (obs, latent) index lists per window.
 
     ``known_video`` (B, T, C, H, W) with ``known_mask`` (B, T, H, W), both or neither (not in the reference): the part of
@@ -58,6 +60,9 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     use_dpm_solver = bool(getattr(args, "use_dpm_solver", False))
     if use_dpm_solver and getattr(args, "use_ddim", False):
         raise ValueError("use_ddim and use_dpm_solver select different samplers: set one of them")
+    thr = resolve_dynamic_threshold(args)
+    if thr is not None:      # before the first window: the samplers read the setting when they are built
+        diffusion.set_dynamic_threshold(**thr)
     device = th.device(args.device)
     samples = th.zeros_like(batch, device=device)
     samples[:, :args.n_obs] = batch[:, :args.n_obs].to(device)
@@ -111,11 +116,25 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     return samples.to(batch.device), indices_used
 
 
+def resolve_dynamic_threshold(args):
+    """``args.dynamic_threshold`` (with ``args.dynamic_threshold_max``) > LFVDM_DYNAMIC_THRESHOLD > None (leave the diffusion
+    object as it is) -> the keyword arguments of ``GaussianDiffusion.set_dynamic_threshold``, or None."""
+    import os
+    from .gaussian_diffusion import parse_dynamic_threshold
+    pct = getattr(args, "dynamic_threshold", None)
+    if pct is not None:
+        return {"percentile": pct, "max_value": getattr(args, "dynamic_threshold_max", None)}
+    if getattr(args, "dynamic_threshold_max", None) is not None:
+        raise ValueError("dynamic_threshold_max needs dynamic_threshold")
+    spec = os.environ.get("LFVDM_DYNAMIC_THRESHOLD")
+    return None if spec is None else parse_dynamic_threshold(spec)
+
+
 def default_sampling_args(**kw):
     """Namespace with the defaults of the reference CLI (video_sample.py:171-192) for programmatic use."""
     d = dict(sampling_scheme="autoreg", n_obs=36, max_frames=20, max_latent_frames=None, clip_denoised=True,
              optimality=None, eval_dir=None, use_ddim=False, ddim_eta=0.0, use_dpm_solver=False,
-             device="cuda" if th.cuda.is_available() else "cpu")
+             dynamic_threshold=None, dynamic_threshold_max=None, device="cuda" if th.cuda.is_available() else "cpu")
     d.update(kw)
     if d["use_ddim"] and d["use_dpm_solver"]:
         raise ValueError("use_ddim and use_dpm_solver select different samplers: set one of them")
