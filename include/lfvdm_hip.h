@@ -670,6 +670,35 @@ int lfvdm_dyn_threshold(const float* x, const float* model_out, const int64_t* t
                         const float* sqrt_recipm1_acp, int mean_type, int x0hat_fma, const float* frame_mask, int B, int T,
                         int64_t frame_inner, double percentile, float max_value, float* xhat, float* stats, void* workspace,
                         void* stream);
+/* Temporally correlated noise prior (the mixed / progressive priors of PYoCo, Ge et al. 2023, defined on the frame INDICES
+ * of a window; not in the reference; csrc/noise_prior.hip).  Per sample b with frame indices f_0 .. f_{T-1} (any order,
+ * repeats allowed) the noise over frames at a fixed (channel, y, x) is Gaussian with covariance
+ *     K_ij = a + c rho^|f_i - f_j| + (1 - a - c) [i == j],   K_ii = 1 exactly,
+ * independent across (channel, y, x) and across samples: noise = L xi, L the lower Cholesky factor of K, xi i.i.d. N(0, 1).
+ *   lfvdm_noise_prior_factor   one workgroup per sample; K (rho^|f_i - f_j| by pow in fp64, the gap taken exactly in 64
+ *                       bits: a huge gap underflows to 0) and the column-by-column Cholesky in fp64 in LDS:
+ *                           d_j = K_jj - sum_{k<j} L_jk^2;  d_j < 1e-12: column j of L is zero (a repeated frame under
+ *                           a + c = 1 then receives its twin's noise, and nothing becomes NaN);
+ *                           otherwise L_ij = (K_ij - sum_{k<j} L_ik L_jk) / sqrt(d_j) for i >= j (the diagonal as well).
+ *                       L_out (B, T, T) fp32, row-major, the strict upper triangle written as 0.  a, c >= 0, a + c <= 1
+ *                       (up to 1e-12: the independent part is max(0, 1 - a - c)), 0 <= rho < 1.
+ *   lfvdm_noise_prior_fill     out (B, T, E), E = C * H * W elements per frame.
+ *                       mix mode (xi != NULL, (B, T, E)):  out[b][i][e] = sum_{j <= i} L[b][i][j] xi[b][j][e], one fp32 fmaf
+ *                       per term onto +0 in ascending j: bitwise reproducible and independent of the launch geometry.  out may
+ *                       equal xi (in place): one workgroup owns ALL T frames of its tile of elements of one sample, stages
+ *                       them in LDS and meets a barrier before its first store, and no other workgroup touches that tile.
+ *                       Partial overlap of out and xi is not allowed.  seed and t are not read.
+ *                       draw mode (xi == NULL): xi is drawn in the kernel with the Philox construction of lfvdm_update_rng_x0
+ *                       on a stream of its own - key seed[0] (both words), counter (quad index within the row of T * E
+ *                       elements, batch row b, t[b], 4) - so with L = I the output is the stream-4 sibling of the update
+ *                       entries' noise.  E must be a multiple of 4 and out 16-byte aligned.
+ * A NULL required pointer (seed and t in draw mode), B outside [1, 65535], T outside [1, 64], E < 1, T * E above 2^31 - 1,
+ * a, c or rho outside their ranges (or NaN), or draw mode with E % 4 != 0 or a misaligned out -> LFVDM_E_SHAPE, before anything
+ * is launched: out is not written.  Mix mode takes any E (16-byte accesses where E % 4 == 0 and both pointers are aligned). */
+int lfvdm_noise_prior_factor(const int64_t* frame_indices, double a, double c, double rho, float* L_out, int B, int T,
+                             void* stream);
+int lfvdm_noise_prior_fill(const float* L, const float* xi, const int64_t* seed, const int64_t* t, float* out, int B, int T,
+                           int64_t E, void* stream);
 /* Sampler clock of the captured denoising step (the loop `for i in indices: t = th.tensor([i]*B)` of
  * gaussian_diffusion.py:509-512 and _WrappedModel's timestep map, respace.py:117-122, kept on the device):
  * t[b] <- max(t[b] - 1, 0);  model_t[b] <- model_timestep_table[t[b]]. */

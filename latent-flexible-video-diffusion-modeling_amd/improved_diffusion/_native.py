@@ -146,6 +146,8 @@ _SIGS = {
     "lfvdm_renoise": ([c_fp] * 6 + [c_i, c_i, c_fp], c_i),
     "lfvdm_dyn_threshold_workspace": ([c_i, C.c_int64, C.POINTER(C.c_size_t)], c_i),
     "lfvdm_dyn_threshold": ([c_fp] * 5 + [c_i, c_i, c_fp, c_i, c_i, C.c_int64, C.c_double, C.c_float] + [c_fp] * 4, c_i),
+    "lfvdm_noise_prior_factor": ([c_fp, C.c_double, C.c_double, C.c_double, c_fp, c_i, c_i, c_fp], c_i),
+    "lfvdm_noise_prior_fill": ([c_fp] * 5 + [c_i, c_i, C.c_int64, c_fp], c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_vb_terms": ([c_fp] * 12 + [c_i, c_i] + [c_fp] * 4 + [c_i] * 5 + [c_fp], c_i),
     "lfvdm_vb_terms_bwd": ([c_fp] * 11 + [c_i, c_i, c_fp, c_i, c_i, c_i, c_fp], c_i),
@@ -794,6 +796,30 @@ def dyn_threshold(x, out, t, recip, recipm1, mean_type, x0hat_fma, frame_mask, p
                                     int(bool(x0hat_fma)), ptr(frame_mask), B, T, x.numel() // (B * T), float(percentile),
                                     float("inf") if max_value is None else float(max_value), ptr(xhat), ptr(stats),
                                     ptr(workspace, torch.uint8), stream()), "lfvdm_dyn_threshold")
+
+
+def noise_prior_factor(frame_indices, a, c, rho, out=None):
+    """The lower Cholesky factor of the noise prior's covariance per sample (lfvdm_noise_prior_factor): ``frame_indices``
+    (B, T) int64 -> L (B, T, T) fp32, the strict upper triangle 0.  ``out``: a static buffer to write instead."""
+    B, T = frame_indices.shape
+    L = torch.empty(B, T, T, device=frame_indices.device) if out is None else out
+    if L.numel() != B * T * T:
+        raise RuntimeError("noise_prior_factor: L is (B, T, T)")
+    check(lib().lfvdm_noise_prior_factor(ptr(frame_indices, torch.int64), float(a), float(c), float(rho), ptr(L), B, T, stream()),
+          "lfvdm_noise_prior_factor")
+    return L
+
+
+def noise_prior_fill(L, out, xi=None, seed=None, t=None):
+    """out (B, T, ...) <- L xi along the frame axis (lfvdm_noise_prior_fill).  ``xi`` given (it may be ``out``): mix mode.
+    ``xi`` None: xi is drawn in the kernel under ``seed`` (one int64) at the rows' timesteps ``t`` (B,), Philox stream 4."""
+    B, T = out.shape[0], out.shape[1]
+    if L.numel() != B * T * T or (xi is not None and xi.shape != out.shape):
+        raise RuntimeError("noise_prior_fill: L is (B, T, T), xi is shaped like out (B, T, ...)")
+    if xi is None and (seed is None or t is None or t.numel() != B):
+        raise RuntimeError("noise_prior_fill: draw mode needs seed and t (B,)")
+    check(lib().lfvdm_noise_prior_fill(ptr(L), ptr(xi), ptr(seed, torch.int64), ptr(t, torch.int64), ptr(out), B, T,
+                                       out.numel() // (B * T), stream()), "lfvdm_noise_prior_fill")
 
 
 def vb_terms(x_start, x_t, out, noise, t, recip, recipm1, c1, c2, post_logvar, model_logvar, mask, mean_type, clip, vb,

@@ -172,6 +172,16 @@ class GraphSampler(ReplayedStep):
             self.dyn_stats = th.zeros(B, 3, device=dev)
             self.dyn_ws = th.zeros(nat.dyn_threshold_workspace(B, self.xhat[0].numel()), dtype=th.uint8, device=dev)
             self.frame_mask = th.ones(B, T, device=dev)
+        # temporally correlated noise prior (GaussianDiffusion.set_noise_prior), read ONCE here like the threshold - it is
+        # part of the sampler cache key.  begin() uploads the window's frame indices and factors their covariance once per
+        # chain, outside the graph (lfvdm_noise_prior_factor); the captured step of a stochastic rule then draws L xi into
+        # ``noise`` with one launch (lfvdm_noise_prior_fill) in front of the unfused, unchanged update
+        self.prior = diffusion.noise_prior
+        self.prior_frames = self.prior_L = None
+        if self.prior is not None:
+            B, T = self.shape[:2]
+            self.prior_frames = th.zeros(B, T, dtype=th.int64, device=dev)
+            self.prior_L = th.zeros(B, T, T, device=dev)
         self.noise = th.empty(self.shape, device=dev)
         # the step's x0-hat; under the multistep rule also the history the next step reads (in and out of one launch)
         self.pred = th.empty(self.shape, device=dev)
@@ -234,7 +244,11 @@ class GraphSampler(ReplayedStep):
         # under dynamic thresholding the head conv is never fused with the update (the branch of LFVDM_FUSED_HEAD=0, whatever
         # the environment says): the quantile needs the whole x0-hat before any element can be updated
         dyn = self.threshold is not None
-        fused = (not dyn and os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
+        # a noise prior takes the same branch where the step draws noise at all: L xi needs its own launch, which writes
+        # ``noise`` for lfvdm_update_x0.  The deterministic rules launch nothing extra (only x_T carries the prior), and noise
+        # the caller injects is used as given
+        prior = self.prior is not None and not det and not self.inject_noise
+        fused = (not dyn and not prior and os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
                  and pl.fuse_head_update(self.t_buf, self.tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
                                          ddim=self.ddim, predict_xstart=self.x0_mode))
         # device-side clock: t <- max(t - 1, 0), model timestep <- table[t]  (t_buf holds "previous t"); with timestep
@@ -247,8 +261,8 @@ class GraphSampler(ReplayedStep):
             pl.launch()
         draw = not (fused or in_kernel or self.inject_noise)
         # launches of a step beside the plan's own (bench.py reports launches per step): the clock, the update, the draw
-        # (+ the four launches of the dynamic threshold)
-        self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw) + (4 if dyn else 0)
+        # (+ the four launches of the dynamic threshold, + the fill of the noise prior)
+        self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw) + (4 if dyn else 0) + int(prior)
         if fused:
             return
         out, clip = pl.out, self.clip
@@ -260,6 +274,15 @@ class GraphSampler(ReplayedStep):
         if self.multistep:
             nat.update_ms_x0(pl.x_in, out, self.pred, self.t_buf, recip, recipm1, c1, c2, sg, mean_type, clip, pl.x_in,
                              self.pred)
+            return
+        if prior:
+            if draw:      # LFVDM_SAMPLER_NOISE=torch: torch's draw, mixed in place
+                self.noise.normal_()
+                nat.noise_prior_fill(self.prior_L, self.noise, xi=self.noise)
+            else:         # xi drawn in the kernel: the chain's key, this step's timesteps, a Philox stream of its own
+                nat.noise_prior_fill(self.prior_L, self.noise, seed=self.seed, t=self.t_buf)
+            nat.update_x0(pl.x_in, out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, clip, pl.x_in,
+                          self.pred)
             return
         if in_kernel:
             nat.update_rng_x0(pl.x_in, out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
@@ -289,6 +312,9 @@ class GraphSampler(ReplayedStep):
                 self.frame_mask.fill_(1.0)
             else:
                 self.frame_mask.copy_(lm.reshape(self.frame_mask.shape))
+        if self.prior is not None:           # this window's factor L, once per chain and before the (first chain's) capture
+            self.prior_frames.copy_(model_kwargs["frame_indices"].reshape(self.prior_frames.shape))
+            nat.noise_prior_factor(self.prior_frames, *self.prior, out=self.prior_L)
         self._begin_chain(img, model_kwargs)
         self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
         if self.multistep:

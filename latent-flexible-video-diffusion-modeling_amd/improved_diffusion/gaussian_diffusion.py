@@ -39,7 +39,12 @@ What is native here
     reference) in every sampler: four HIP launches (csrc/dyn_threshold.hip, an exact radix select of the per-sample
     quantile of |x0-hat| over the window's latent frames) write the thresholded x0-hat, which the step's usual update
     launch consumes as the output of an x0-prediction model; the replayed step keeps its graph, its in-kernel noise and the
-    known-region blend.  Off by default; its effect on sample quality has not been measured.
+    known-region blend.  Off by default; its effect on sample quality has not been measured;
+  * a temporally correlated noise prior (``set_noise_prior``, ``noise_prior.py``; PYoCo's mixed / progressive priors
+    defined on a window's frame indices - not in the reference): noise = L xi with L the Cholesky factor of the per-sample
+    frame covariance (csrc/noise_prior.hip: the factor once per chain, one fill launch in front of the un-fused update of
+    a stochastic replayed step), for training noise, x_T and the per-step draws.  Off by default; its effect on sample
+    quality has not been measured.
 
 Out of scope (not reached by the default CLIs): learned sigma (``learn_sigma=True``, also together with
 ``use_kl``: the reference's own 5-D code path asserts on it, so there is no behaviour to match),
@@ -242,6 +247,7 @@ class GaussianDiffusion:
         self._dyn_ws = {}              # (device, B) -> the eager steps' threshold workspace
         self.last_threshold_stats = None
         self.set_dynamic_threshold()
+        self._noise_prior = None       # (a, c, rho) of set_noise_prior, or None: independent noise, today's paths
         self.setup_enc_dec()
 
     # ------------------------------------------------------------------ tables on device
@@ -506,6 +512,54 @@ class GaussianDiffusion:
             raise ValueError(f"latent_mask holds one value per frame (B, T) = {(B, T)}, got {tuple(latent_mask.shape)}")
         return latent_mask.to(device=x.device, dtype=th.float32).reshape(B, T).contiguous()
 
+    # ------------------------------------------------------------------ temporally correlated noise prior (not in the reference)
+    def set_noise_prior(self, spec=None):
+        """Draw the noise of training and sampling correlated along time (``noise_prior``: the mixed / progressive priors
+        of PYoCo, Ge et al. 2023, defined on a window's frame indices).  ``spec``: "mixed:ALPHA", "progressive:ALPHA",
+        "cov:A:C:RHO", an (a, c, rho) triple, or None / "none" (the default): independent noise, exactly the code paths,
+        launch counts and noise streams there always were.
+
+        With a prior set, ``training_losses(noise=None)``, the initial x_T of every sampling loop called with
+        ``noise=None`` and the per-step draws of ``p_sample`` / ``ddim_sample`` are ``apply_noise_prior(th.randn_like(x),
+        model_kwargs["frame_indices"], prior)`` - ``th.manual_seed`` still fixes them - and the replayed ancestral /
+        stochastic DDIM step draws L xi with one launch of its own (lfvdm_noise_prior_fill on Philox stream 4) in front of
+        the unchanged update; the deterministic rules carry the prior in x_T alone.  Noise the caller passes in is used as
+        given.  Every frame stays marginally N(0, 1): the schedule tables and update rules are untouched.  Without
+        ``frame_indices`` in ``model_kwargs``: ValueError.
+
+        The variational bound (KL losses, ``calc_bpd_loop[_subsampled]``), the schedule search and known-region sampling
+        assume independent noise: a KL ``loss_type`` raises here, the others raise NotImplementedError before any work.  A
+        correlated forward process for the known region is a follow-up.  The effect of a prior on the sample quality of a
+        trained model has not been measured."""
+        from .noise_prior import parse_noise_prior
+        prior = parse_noise_prior(spec)
+        if prior is not None and self.loss_type.is_vb():
+            raise ValueError(f"noise prior {spec!r}: the variational bound of {self.loss_type} assumes independent noise - a "
+                             "prior goes with the MSE losses")
+        self._noise_prior = prior
+
+    @property
+    def noise_prior(self):
+        """(a, c, rho) in force, or None: independent noise."""
+        return self._noise_prior
+
+    def _prior_noise(self, xi, model_kwargs):
+        """``xi`` (an i.i.d. draw) -> the draw under the prior in force; ``xi`` itself without one."""
+        if self._noise_prior is None:
+            return xi
+        from .noise_prior import apply_noise_prior
+        fi = None if model_kwargs is None else model_kwargs.get("frame_indices")
+        if fi is None:
+            raise ValueError("a noise prior is set (set_noise_prior): model_kwargs['frame_indices'] is needed to draw noise")
+        return apply_noise_prior(xi, fi, self._noise_prior)
+
+    def _refuse_noise_prior(self, what):
+        """What the paths that assume independent noise do first."""
+        if self._noise_prior is not None:
+            from .noise_prior import format_noise_prior
+            raise NotImplementedError(f"{what} assumes independent noise; the noise prior {format_noise_prior(self._noise_prior)!r} "
+                                      "is set (set_noise_prior(None) turns it off)")
+
     def _gather(self, name, t, ndim):
         return _bshape(self.tables(t.device)[name][t], ndim)
 
@@ -691,7 +745,7 @@ class GaussianDiffusion:
         model_kwargs = model_kwargs or {}
         eps, attn = model(x, self._scale_timesteps(t), return_attn_weights=return_attn_weights, **model_kwargs)
         if noise is None:
-            noise = th.randn_like(x)
+            noise = self._prior_noise(th.randn_like(x), model_kwargs)
         if denoised_fn is not None:
             sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn,
                                                     latent_mask=model_kwargs.get("latent_mask"))
@@ -783,7 +837,8 @@ class GaussianDiffusion:
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)      # torch's generator, before anything else
+        # torch's generator, before anything else; under a noise prior the chain starts from L xi
+        img = noise if noise is not None else self._prior_noise(th.randn(*shape, device=device), model_kwargs)
         repeats, gen, eps = 1, None, None
         if known is not None:      # a private generator (torch's own is not advanced): the fixed eps, the slow path's draws
             repeats = known.repeats
@@ -882,7 +937,7 @@ class GaussianDiffusion:
         assert t.shape == (x.shape[0],)
         eps, _ = model(x, self._scale_timesteps(t), return_attn_weights=False, **model_kwargs)
         if float(eta) != 0.0 and noise is None:
-            noise = th.randn_like(x)
+            noise = self._prior_noise(th.randn_like(x), model_kwargs)
         if denoised_fn is not None:
             sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn, ("ddim", eta), reverse,
                                                     latent_mask=model_kwargs.get("latent_mask"))
@@ -969,8 +1024,9 @@ class GaussianDiffusion:
     def _graph_sampler(self, unet, shape, clip_denoised, rule=("ancestral",)):
         # the update rule is part of the key (appended: position 1 stays the shape): a DDIM chain and an ancestral chain on
         # the same shape never share a captured graph
-        # and so is the dynamic threshold in force (last; None: the static clamp): the sampler reads it when it is built
-        key = (id(unet), shape, bool(clip_denoised), tuple(rule), self._threshold(clip_denoised))
+        # and so is the dynamic threshold in force (last; None: the static clamp): the sampler reads it when it is built; and so
+        # is the noise prior in force (in front of it; None: independent noise).  Known-region samplers never run under a prior
+        key = (id(unet), shape, bool(clip_denoised), tuple(rule), self._noise_prior, self._threshold(clip_denoised))
         return self._cached_sampler(self._samplers, key, unet, shape, clip_denoised, rule)
 
     # ------------------------------------------------------------------ known-region sampling (RePaint; not in the reference)
@@ -1068,6 +1124,9 @@ class GaussianDiffusion:
 
     def _known_region_chain(self, model, shape, known, known_mask, sampler, eta, resample_steps, noise, clip_denoised,
                             denoised_fn, model_kwargs, latent_mask, device, progress, _reuse_buffers=False, _final_only=False):
+        # the blend puts the known part back with INDEPENDENT noise at every level; a forward process correlated along
+        # time for the known region is a follow-up
+        self._refuse_noise_prior("known-region sampling")
         rule, fixed, repeats = self._known_region_check(shape, known, known_mask, sampler, eta, resample_steps, noise, latent_mask)
         if device is None:
             device = next(model.parameters()).device
@@ -1105,7 +1164,7 @@ class GaussianDiffusion:
             raise NotImplementedError(self.loss_type)
         model_kwargs = model_kwargs or {}
         if noise is None:
-            noise = th.randn_like(x_start)
+            noise = self._prior_noise(th.randn_like(x_start), model_kwargs)
         x_t = self.q_sample(x_start, t, noise=noise)
         if self.loss_type.is_vb():
             loss = self._vb_terms(model, x_start, x_t, t, False, model_kwargs, None)["output"]
@@ -1198,6 +1257,7 @@ class GaussianDiffusion:
         The full descending walk of a native U-Net on the device with ``model_kwargs`` given replays one captured hipGraph
         per step (``BpdEvaluator``); everything else runs one model call and one fused launch per step."""
         from .unet import UNetVideoModel
+        self._refuse_noise_prior("the variational bound (calc_bpd_loop / calc_bpd_loop_subsampled)")
         B = x_start.shape[0]
         full = list(range(self.num_timesteps))[::-1]
         if t_seq is None:

@@ -132,6 +132,8 @@ def _refuse(scheme, diffusion):
     if diffusion.model_var_type not in (ModelVarType.FIXED_LARGE, ModelVarType.FIXED_SMALL):
         raise NotImplementedError("the search scores with the fixed-sigma variational-bound terms: learned sigma "
                                   "(learn_sigma=True) is not supported")
+    # the scores are variational-bound terms under independent noise keyed by video frame (set_noise_prior's docstring)
+    diffusion._refuse_noise_prior("the schedule search (find_optimal_schedule)")
 
 
 # ---------------------------------------------------------------------------------------------- native backend

@@ -72,6 +72,20 @@ def resolve_loss_weighting(keyword=None, args=None):
     return parse_loss_weighting("none" if value is None else value)
 
 
+def resolve_noise_prior(keyword=None, args=None):
+    """Noise prior of ``TrainLoop``, resolved as ``loss_weighting`` is: the ``noise_prior`` keyword, else
+    ``args.noise_prior``, else the environment's LFVDM_NOISE_PRIOR -> the spec in its canonical text ("none", or
+    "cov:a:c:rho" of ``noise_prior.format_noise_prior``); none of the three: None, the diffusion object keeps its setting.
+    Malformed: ValueError."""
+    from .noise_prior import format_noise_prior
+    value = keyword
+    if value is None:
+        value = getattr(args, "noise_prior", None)
+    if value is None:
+        value = os.environ.get("LFVDM_NOISE_PRIOR") or None
+    return None if value is None else format_noise_prior(value)
+
+
 class ParamArena:
     """Flat fp32 storage for a list of parameters: ``p.data`` and ``p.grad`` become views of two
     contiguous buffers, which gives one collective per bucket, one fused optimizer launch and a memset for
@@ -119,13 +133,19 @@ class TrainLoop:
     def __init__(self, *, model, diffusion, data, batch_size, microbatch, lr, ema_rate, log_interval, save_interval,
                  resume_checkpoint, use_fp16, diffusion_space_kwargs, fp16_scale_growth, schedule_sampler, weight_decay,
                  lr_anneal_steps, sample_interval, pad_with_random_frames, max_frames, enc_dec_chunk_size, args,
-                 max_grad_norm=None, loss_weighting=None):
+                 noise_prior=None, max_grad_norm=None, loss_weighting=None):
         if use_fp16:
             raise NotImplementedError("use_fp16 is off in the reference defaults; the native path is fp32")
         self.args = args
         self.max_grad_norm = resolve_max_grad_norm(max_grad_norm, args)     # 0: no clipping, no non-finite skip
         diffusion.set_loss_weighting(**resolve_loss_weighting(loss_weighting, args))     # validated here; "none": today's path
         self.loss_weighting = diffusion.loss_weighting
+        # the training noise is drawn under this prior (training_losses); the spec is saved with the checkpoint's config
+        given = resolve_noise_prior(noise_prior, args)
+        if given is not None:
+            diffusion.set_noise_prior(given)
+        from .noise_prior import format_noise_prior
+        self.noise_prior = format_noise_prior(diffusion.noise_prior)
         dist_util.limit_host_threads()
         self.model = model
         self.diffusion = diffusion
@@ -799,7 +819,7 @@ class TrainLoop:
             def save_checkpoint(rate, params):
                 print(f"saving model {rate}...")
                 name = f"model{self.step:06d}.pt" if not rate else f"ema_{rate}_{self.step:06d}.pt"
-                th.save({"state_dict": self._master_params_to_state_dict(params), "config": self.args.__dict__,
+                th.save({"state_dict": self._master_params_to_state_dict(params), "config": self._checkpoint_config(),
                          "step": self.step}, os.path.join(get_blob_logdir(self.args), name))
 
             save_checkpoint(0, self.master_params)
@@ -808,6 +828,11 @@ class TrainLoop:
             th.save(self.opt.state_dict(), os.path.join(get_blob_logdir(self.args), f"opt{self.step:06d}.pt"))
         if dist.is_initialized():
             dist.barrier()
+
+    def _checkpoint_config(self):
+        """The arguments as saved with a checkpoint, plus the noise prior the run trains under (however it was given): a
+        sampler compares it with its own (``video_sampler.warn_noise_prior_mismatch``)."""
+        return dict(self.args.__dict__, noise_prior=self.noise_prior)
 
     def _master_params_to_state_dict(self, master_params):
         sd = self.model.state_dict()

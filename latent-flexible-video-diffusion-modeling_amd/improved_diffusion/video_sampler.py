@@ -41,7 +41,10 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     chain; in the reference ``--use_ddim`` only renames the results folder, here it selects the sampler), use_dpm_solver
     (DPM-Solver++(2M) instead; together with use_ddim: ValueError), dynamic_threshold / dynamic_threshold_max (a percentile
     and an optional cap: ``diffusion.set_dynamic_threshold`` is called with them before the first window; without the
-    attribute, LFVDM_DYNAMIC_THRESHOLD="0.995" or "0.995:1.5" is read; neither: the diffusion's setting stays).  Returns ``(samples, indices_used)``
+    attribute, LFVDM_DYNAMIC_THRESHOLD="0.995" or "0.995:1.5" is read; neither: the diffusion's setting stays), noise_prior (a spec
+    of ``noise_prior.parse_noise_prior`` for ``diffusion.set_noise_prior``, else LFVDM_NOISE_PRIOR, resolved the same way;
+    ``trained_noise_prior``, the spec in the checkpoint's config, is compared with it and a difference is logged; a prior
+    together with known_video: NotImplementedError).  Returns ``(samples, indices_used)``
     with ``samples`` on batch's device and ``indices_used`` the list of (obs, latent) index lists per window.
 
     ``known_video`` (B, T, C, H, W) with ``known_mask`` (B, T, H, W), both or neither (not in the reference): the part of
@@ -63,6 +66,11 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     thr = resolve_dynamic_threshold(args)
     if thr is not None:      # before the first window: the samplers read the setting when they are built
         diffusion.set_dynamic_threshold(**thr)
+    prior = resolve_noise_prior(args)
+    if prior is not None:    # likewise; "none" turns a prior off, no setting at all leaves the diffusion object as it is
+        diffusion.set_noise_prior(prior)
+    if getattr(args, "trained_noise_prior", None) is not None:
+        warn_noise_prior_mismatch(args.trained_noise_prior, diffusion.noise_prior)
     device = th.device(args.device)
     samples = th.zeros_like(batch, device=device)
     samples[:, :args.n_obs] = batch[:, :args.n_obs].to(device)
@@ -130,11 +138,40 @@ def resolve_dynamic_threshold(args):
     return None if spec is None else parse_dynamic_threshold(spec)
 
 
+def resolve_noise_prior(args):
+    """``args.noise_prior`` > LFVDM_NOISE_PRIOR > None (leave the diffusion object as it is) -> the spec for
+    ``GaussianDiffusion.set_noise_prior`` ("none" included: it turns a prior off), or None.  Malformed: ValueError."""
+    import os
+    from .noise_prior import parse_noise_prior
+    spec = getattr(args, "noise_prior", None)
+    if spec is None:
+        spec = os.environ.get("LFVDM_NOISE_PRIOR")
+    if spec is None:
+        return None
+    parse_noise_prior(spec)
+    return spec
+
+
+def warn_noise_prior_mismatch(trained, sampling):
+    """A checkpoint records the prior it was trained with (``config["noise_prior"]``; a caller hands it over as
+    ``args.trained_noise_prior``).  Sampling it under another prior is allowed - and said in the log.  -> whether it warned."""
+    import logging
+    from .noise_prior import format_noise_prior, parse_noise_prior
+    if trained is None:
+        return False
+    a, b = parse_noise_prior(trained), parse_noise_prior(sampling)
+    if a == b:
+        return False
+    logging.getLogger("improved_diffusion").warning(
+        "the checkpoint was trained with the noise prior %r and is sampled with %r", format_noise_prior(a), format_noise_prior(b))
+    return True
+
+
 def default_sampling_args(**kw):
     """Namespace with the defaults of the reference CLI (video_sample.py:171-192) for programmatic use."""
     d = dict(sampling_scheme="autoreg", n_obs=36, max_frames=20, max_latent_frames=None, clip_denoised=True,
              optimality=None, eval_dir=None, use_ddim=False, ddim_eta=0.0, use_dpm_solver=False,
-             dynamic_threshold=None, dynamic_threshold_max=None, device="cuda" if th.cuda.is_available() else "cpu")
+             dynamic_threshold=None, dynamic_threshold_max=None, noise_prior=None, device="cuda" if th.cuda.is_available() else "cpu")
     d.update(kw)
     if d["use_ddim"] and d["use_dpm_solver"]:
         raise ValueError("use_ddim and use_dpm_solver select different samplers: set one of them")
