@@ -792,6 +792,28 @@ int lfvdm_frame_metrics(const void* pred, const void* truth, int dtype, float sc
 /* floats of `partials` the launch above needs; 0 for a shape it refuses */
 long lfvdm_frame_metrics_workspace(int K, int N, int C, int H, int W);
 
+/* Frame distances and farthest-point selection behind the adaptive sampling schemes (csrc/frame_select.hip).
+ *   x [B][T][C][H][W] float32 (generic vectors of D floats: C = D, H = W = 1, L = 1);  dist [B][T][T] float32.
+ *   d_L(a, b) = (1 / L) sum_{l < L} mean((P_l(a - b))^2), P_0 = identity, P_l = 2^l x 2^l average pooling, L in 1..3,
+ *   all levels from one pass over the difference (never the Gram form), fixed summation order, no atomics.
+ * lfvdm_frame_dist_rows: for every video b, every i in new_idx[0..n_new) and every j in new_idx ++ cand_idx[0..n_cand) it writes
+ *   dist[b][i][j] and dist[b][j][i] (the same bits; exactly 0 for i == j) and nothing else.  The lists are DEVICE int32, shared by
+ *   the videos, in any order, and may repeat or overlap; the value of a pair depends on the two frames and L alone, not on the
+ *   launch, the tile or the list position.  An index outside [0, T) is skipped (nothing read, nothing written).  n_cand may be 0
+ *   (cand_idx NULL).  L outside 1..3, H or W no multiple of 2^(L-1), a non-positive size, n_new <= 0, B or T > 65535, more than
+ *   2^31 - 1 elements per frame, a NULL pointer -> LFVDM_E_SHAPE, before anything is launched.
+ * lfvdm_fps_select: greedy farthest-point selection, one workgroup per video, all picks in one launch.  cand_idx: n_cand frame
+ *   indices; forced_pos: n_forced >= 1 POSITIONS into cand_idx; picks [B][n] int32 positions into cand_idx:
+ *     picks[0] = forced[0];  for i = 1..n-1:  min_d = min(min_d, dist[b][cand[picks[i-1]]][cand[:]]) starting from +inf,
+ *     picks[i] = forced[i] if i < n_forced, else the LOWEST position of the maximum of min_d (numpy's argmax, NaN included).
+ *   n > n_cand repeats positions exactly as that loop does.  A forced position outside [0, n_cand) or a chosen frame outside
+ *   [0, T) makes that pick and every later one -1; any other candidate outside [0, T) reads as distance 0.  Non-positive sizes,
+ *   T > 65535, a NULL pointer -> LFVDM_E_SHAPE; n_cand > 4096 (min_d lives in LDS) -> LFVDM_E_UNSUPPORTED; nothing is launched. */
+int lfvdm_frame_dist_rows(const float* x, int B, int T, int C, int H, int W, int L, const int32_t* new_idx, int n_new,
+                          const int32_t* cand_idx, int n_cand, float* dist, void* stream);
+int lfvdm_fps_select(const float* dist, int B, int T, const int32_t* cand_idx, int n_cand, const int32_t* forced_pos, int n_forced,
+                     int n, int32_t* picks, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Fused AdamW + EMA + gradient-norm over one flat fp32 arena (train_util.py:346-357, nn.py:55-65).
  * torch.optim.AdamW semantics (decoupled weight decay, bias correction); ema <- rate*ema + (1-rate)*p.

@@ -153,6 +153,8 @@ _SIGS = {
     "lfvdm_vb_terms_bwd": ([c_fp] * 11 + [c_i, c_i, c_fp, c_i, c_i, c_i, c_fp], c_i),
     "lfvdm_frame_metrics": ([c_fp, c_fp, c_i, C.c_float, C.c_float] + [c_i] * 5 + [c_fp, c_fp, c_fp, C.c_long, c_fp], c_i),
     "lfvdm_frame_metrics_workspace": ([c_i] * 5, C.c_long),
+    "lfvdm_frame_dist_rows": ([c_fp] + [c_i] * 6 + [c_fp, c_i, c_fp, c_i, c_fp, c_fp], c_i),
+    "lfvdm_fps_select": ([c_fp, c_i, c_i, c_fp, c_i, c_fp, c_i, c_i, c_fp, c_fp], c_i),
     "lfvdm_gn_bwd_stats": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp], c_i),
     "lfvdm_gn_bwd_apply": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_gn_bwd_apply_params": ([c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i,
@@ -862,6 +864,27 @@ def frame_metrics(pred, truth, scale, shift, K, N, C, H, W, mse, ssim, partials)
         raise RuntimeError("frame_metrics: tensor sizes do not match (K, N, C, H, W)")
     check(lib().lfvdm_frame_metrics(ptr(pred, dt), ptr(truth, dt), _PIX[dt], float(scale), float(shift), K, N, C, H, W, ptr(mse),
                                     ptr(ssim), ptr(partials), partials.numel(), stream()), "lfvdm_frame_metrics")
+
+
+def frame_dist_rows(x, B, T, C, H, W, levels, new_idx, cand_idx, dist):
+    """dist (B, T, T) float32 <- the ``levels``-level distance of every frame in ``new_idx`` to every frame in ``new_idx`` and
+    ``cand_idx`` (device int32 lists; ``cand_idx`` None or empty: none), rows and columns, of ``x`` (B, T, C, H, W) float32
+    (lfvdm_frame_dist_rows)."""
+    if x.numel() != B * T * C * H * W or dist.numel() != B * T * T:
+        raise RuntimeError("frame_dist_rows: tensor sizes do not match (B, T, C, H, W)")
+    n_cand = 0 if cand_idx is None else cand_idx.numel()
+    check(lib().lfvdm_frame_dist_rows(ptr(x), B, T, C, H, W, int(levels), ptr(new_idx, torch.int32), new_idx.numel(),
+                                      ptr(cand_idx, torch.int32) if n_cand else None, n_cand, ptr(dist), stream()),
+          "lfvdm_frame_dist_rows")
+
+
+def fps_select(dist, B, T, cand_idx, forced_pos, n, picks):
+    """picks (B, n) int32 <- greedy farthest-point positions into ``cand_idx`` (device int32) on ``dist`` (B, T, T), starting
+    from the positions ``forced_pos`` (device int32, at least one) (lfvdm_fps_select)."""
+    if dist.numel() != B * T * T or picks.numel() != B * n:
+        raise RuntimeError("fps_select: tensor sizes do not match (B, T, n)")
+    check(lib().lfvdm_fps_select(ptr(dist), B, T, ptr(cand_idx, torch.int32), cand_idx.numel(), ptr(forced_pos, torch.int32),
+                                 forced_pos.numel(), int(n), ptr(picks, torch.int32), stream()), "lfvdm_fps_select")
 
 
 def prepare_batch(pool, table, batch, frame_indices, obs_mask, latent_mask):

@@ -9,6 +9,8 @@ Schemes:  autoreg · long-range · hierarchy-{2..5} · adaptive-autoreg · adapt
 The adaptive schemes pick the conditioning frames by greedy farthest-point selection in an LPIPS embedding
 (reference :154-182); the LPIPS network needs the `lpips` package and its weights, so they accept any
 ``embed_fn(videos, indices) -> (B, len(indices), D)`` and only fall back to LPIPS when none is given.
+``set_frame_metric("msl2:L")`` selects by a network-free frame distance instead (frame_select.py: cached distances and the
+picks of a window in one launch on the device).
 """
 import numpy as np
 import torch as th
@@ -208,7 +210,9 @@ def _lpips_embed_fn():
     try:
         import lpips
     except ImportError as e:   # pragma: no cover - package absent offline
-        raise ImportError("adaptive sampling schemes need the `lpips` package (or pass embed_fn=...)") from e
+        raise ImportError("adaptive sampling schemes need the `lpips` package (or pass embed_fn=..., or choose the network-free "
+                          "frame metric: adaptive_metric='msl2:1' / LFVDM_ADAPTIVE_METRIC for sample_video, "
+                          "set_frame_metric on the scheme)") from e
 
     class Embedder(lpips.LPIPS):
         def forward(self, x):
@@ -236,10 +240,30 @@ class AdaptiveSamplingSchemeBase(SamplingSchemeBase):
     (reference :232-288)."""
 
     _embed_fn = None
+    _frame_metric = None
 
     def set_embed_fn(self, fn):
         """fn(videos (B,T,C,H,W), indices) -> (B, len(indices), ...); replaces the LPIPS embedding."""
+        if self._frame_metric is not None:
+            raise ValueError("a frame metric is set: the scheme selects by the metric or by an embed_fn, not both")
         self._embed_fn = fn
+
+    def set_frame_metric(self, spec):
+        """Select by the network-free metric ``spec`` ("msl2:L", frame_select.parse_frame_metric) instead of an embedding:
+        distances come from a cache that compares each pair of finished frames once (frame_select.FrameDistanceCache) and the
+        picks of a window from one launch.  This instance's ``select_obs_indices`` is replaced; the embedding route above
+        stays as it is for every scheme that does not call this.  Together with an embed_fn: ValueError."""
+        from .frame_select import FrameDistanceCache, parse_frame_metric
+        if self._embed_fn is not None:
+            raise ValueError("an embed_fn is set: the scheme selects by the metric or by an embed_fn, not both")
+        self._frame_metric = spec
+        self._dist_cache = FrameDistanceCache(parse_frame_metric(spec))
+        self.select_obs_indices = self._select_by_frame_metric
+
+    def _select_by_frame_metric(self, possible_next_indices, n, always_selected=(0,)):
+        from .frame_select import farthest_point_select
+        dist = self._dist_cache.update(self.videos, self._done_frames)
+        return farthest_point_select(dist, possible_next_indices, n, always_selected)
 
     def set_videos(self, videos):
         self.videos = videos
@@ -249,6 +273,8 @@ class AdaptiveSamplingSchemeBase(SamplingSchemeBase):
             self._embed_fn = _lpips_embed_fn()
         return self._embed_fn(self.videos, indices)
 
+    # The embedding route.  set_frame_metric() shadows this method ON THE INSTANCE with _select_by_frame_metric (an instance
+    # attribute wins over the class's and over a subclass's override); next_indices reaches either through self.
     def select_obs_indices(self, possible_next_indices, n, always_selected=(0,)):
         embs = self.embed(possible_next_indices)
         chosen_per_video = []

@@ -15,7 +15,7 @@ from types import SimpleNamespace
 
 import torch as th
 
-from .sampling_schemes import sampling_schemes
+from .sampling_schemes import AdaptiveSamplingSchemeBase, sampling_schemes
 
 
 def window_inputs(samples, obs_frame_indices, latent_frame_indices, device=None):
@@ -44,7 +44,10 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     attribute, LFVDM_DYNAMIC_THRESHOLD="0.995" or "0.995:1.5" is read; neither: the diffusion's setting stays), noise_prior (a spec
     of ``noise_prior.parse_noise_prior`` for ``diffusion.set_noise_prior``, else LFVDM_NOISE_PRIOR, resolved the same way;
     ``trained_noise_prior``, the spec in the checkpoint's config, is compared with it and a difference is logged; a prior
-    together with known_video: NotImplementedError).  Returns ``(samples, indices_used)``
+    together with known_video: NotImplementedError), adaptive_metric (a spec of ``frame_select.parse_frame_metric``, "msl2:1" ..
+    "msl2:3", else LFVDM_ADAPTIVE_METRIC: the adaptive schemes pick their conditioning frames by this network-free frame distance
+    instead of LPIPS; with a non-adaptive scheme: ValueError; on a device the batch must be float32 - other dtypes: ValueError at
+    the first selection - and the running samples are then allocated row-major even for a permuted batch).  Returns ``(samples, indices_used)``
     with ``samples`` on batch's device and ``indices_used`` the list of (obs, latent) index lists per window.
 
     ``known_video`` (B, T, C, H, W) with ``known_mask`` (B, T, H, W), both or neither (not in the reference): the part of
@@ -72,13 +75,22 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     if getattr(args, "trained_noise_prior", None) is not None:
         warn_noise_prior_mismatch(args.trained_noise_prior, diffusion.noise_prior)
     device = th.device(args.device)
-    samples = th.zeros_like(batch, device=device)
+    metric = resolve_adaptive_metric(args)
+    if metric is not None and not issubclass(sampling_schemes[args.sampling_scheme], AdaptiveSamplingSchemeBase):
+        raise ValueError(f"adaptive_metric = {metric!r} is for the adaptive sampling schemes; {args.sampling_scheme!r} chooses its "
+                         "conditioning frames without looking at them")
+    if metric is None:
+        samples = th.zeros_like(batch, device=device)
+    else:      # the distance kernel reads the frames in place: row-major, whatever the strides of a permuted batch
+        samples = th.zeros_like(batch, device=device, memory_format=th.contiguous_format)
     samples[:, :args.n_obs] = batch[:, :args.n_obs].to(device)
     optimality = getattr(args, "optimality", None)
     schedule_path = None if optimality is None else args.eval_dir / "optimal_schedule.pt"
     scheme = iter(sampling_schemes[args.sampling_scheme](
         video_length=T, num_obs=args.n_obs, max_frames=args.max_frames, step_size=args.max_latent_frames,
         optimal_schedule_path=schedule_path))
+    if metric is not None:
+        scheme.set_frame_metric(metric)
     batch_dev = batch.to(device) if just_get_indices else None
     decoded = getattr(diffusion, "diffusion_space", None) in (None, "pixel")
     rows = th.arange(B, device=device)[:, None]
@@ -152,6 +164,20 @@ def resolve_noise_prior(args):
     return spec
 
 
+def resolve_adaptive_metric(args):
+    """``args.adaptive_metric`` > LFVDM_ADAPTIVE_METRIC > None (the adaptive schemes keep their embedding route) -> the spec for
+    ``AdaptiveSamplingSchemeBase.set_frame_metric`` ("msl2:L").  Malformed: ValueError."""
+    import os
+    from .frame_select import parse_frame_metric
+    spec = getattr(args, "adaptive_metric", None)
+    if spec is None:
+        spec = os.environ.get("LFVDM_ADAPTIVE_METRIC")
+    if spec is None:
+        return None
+    parse_frame_metric(spec)
+    return spec
+
+
 def warn_noise_prior_mismatch(trained, sampling):
     """A checkpoint records the prior it was trained with (``config["noise_prior"]``; a caller hands it over as
     ``args.trained_noise_prior``).  Sampling it under another prior is allowed - and said in the log.  -> whether it warned."""
@@ -171,7 +197,8 @@ def default_sampling_args(**kw):
     """Namespace with the defaults of the reference CLI (video_sample.py:171-192) for programmatic use."""
     d = dict(sampling_scheme="autoreg", n_obs=36, max_frames=20, max_latent_frames=None, clip_denoised=True,
              optimality=None, eval_dir=None, use_ddim=False, ddim_eta=0.0, use_dpm_solver=False,
-             dynamic_threshold=None, dynamic_threshold_max=None, noise_prior=None, device="cuda" if th.cuda.is_available() else "cpu")
+             dynamic_threshold=None, dynamic_threshold_max=None, noise_prior=None, adaptive_metric=None,
+             device="cuda" if th.cuda.is_available() else "cpu")
     d.update(kw)
     if d["use_ddim"] and d["use_dpm_solver"]:
         raise ValueError("use_ddim and use_dpm_solver select different samplers: set one of them")
