@@ -670,6 +670,37 @@ int lfvdm_dyn_threshold(const float* x, const float* model_out, const int64_t* t
                         const float* sqrt_recipm1_acp, int mean_type, int x0hat_fma, const float* frame_mask, int B, int T,
                         int64_t frame_inner, double percentile, float max_value, float* xhat, float* stats, void* workspace,
                         void* stream);
+/* Classifier-free guidance on the observed frames (Ho & Salimans 2022) with the rescale of Lin et al. 2024, section 3.4 (not
+ * in the reference; csrc/guidance.hip).  x / xhat are (B, T, frame_inner), out2 is (2 B, T, frame_inner): rows [0, B) the
+ * network output o_c for the window as given, rows [B, 2 B) the output o_u for the same x with obs_mask = 0.  Per batch row
+ * b, t = t[b], every operation rounded to fp32 on its own (no contraction):
+ *     o_g   = o_u + scale (o_c - o_u)
+ *     p(o)  = o (LFVDM_MEAN_X0) | sqrt_recip_acp[t] x - sqrt_recipm1_acp[t] o (LFVDM_MEAN_EPS), the latter in the rounding
+ *             x0hat_fma names, exactly as in lfvdm_dyn_threshold: with o_u == o_c element for element, p(o_g) has the bits
+ *             of the pred_xstart of the update cell
+ *     rescale == 0:  xhat = p(o_g), stats[b] = (0, 0, 1); ONE launch that reads x, o_c, o_u once and writes xhat once;
+ *                    the workspace is not touched (it may be NULL)
+ *     rescale  > 0:  selected elements: those of the frames f with frame_mask[b][f] != 0 (frame_mask == NULL: all);
+ *                    s_c, s_g = the population standard deviations of p(o_c) and p(o_g) over them - per chunk of 4096
+ *                    elements a (count, mean, M2) record accumulated in double by two passes over registers, the records
+ *                    merged by Chan's formula in one fixed order, the root rounded to fp32 once;
+ *                    f = rescale s_c / s_g + (1 - rescale) in fp32 (product, IEEE division, sum);  f = 1 when nothing is
+ *                    selected or s_g == 0;  stats[b] = (s_c, s_g, f);  xhat = p(o_g) f for EVERY element.  Two launches.
+ * xhat then enters lfvdm_dyn_threshold (LFVDM_MEAN_X0) or any update entry above as the output of an x0-prediction model.
+ * No atomics: every byte of xhat and stats is reproducible.  Vector accesses where the pointers are 16-byte aligned and
+ * B * T * frame_inner is a multiple of 4 (the first and last elements of a row that fall off the 16-byte grid are scalar),
+ * scalar ones otherwise; frame_inner need not be a multiple of 4.
+ * workspace: lfvdm_cfg_workspace(B, T * frame_inner) bytes, 8-byte aligned, in ANY state: every word a call reads it has
+ * written before (no memset, hipGraph-capturable, no host synchronisation, no allocation).  One workspace serves one stream
+ * at a time.  NaN inputs are outside the contract.
+ * A NULL x / out2 / t / xhat / stats, a NULL or misaligned workspace with rescale > 0, an unknown mean_type, LFVDM_MEAN_EPS
+ * without its two tables, a negative or non-finite scale, rescale outside [0, 1] (or NaN), B outside [1, 32767], T or
+ * frame_inner <= 0, or T * frame_inner above 2^31 - 1 -> LFVDM_E_SHAPE, before anything is launched. */
+int lfvdm_cfg_workspace(int B, int64_t inner, size_t* bytes);
+int lfvdm_cfg_combine(const float* x, const float* out2, const int64_t* t, const float* sqrt_recip_acp,
+                      const float* sqrt_recipm1_acp, int mean_type, int x0hat_fma, const float* frame_mask, float scale,
+                      float rescale, float* xhat, float* stats, void* workspace, int B, int T, int64_t frame_inner,
+                      void* stream);
 /* Temporally correlated noise prior (the mixed / progressive priors of PYoCo, Ge et al. 2023, defined on the frame INDICES
  * of a window; not in the reference; csrc/noise_prior.hip).  Per sample b with frame indices f_0 .. f_{T-1} (any order,
  * repeats allowed) the noise over frames at a fixed (channel, y, x) is Gaussian with covariance

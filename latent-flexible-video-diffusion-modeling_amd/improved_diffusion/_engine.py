@@ -362,6 +362,7 @@ class Plan:
                                             f"{_table_budget.remaining() / 2 ** 30:.1f} GiB of LFVDM_TIME_TABLE_GB")
             if self.time_table_fallback:
                 self.time_steps = 0
+                self.time_ring = 0      # no tables, no window over them: ensure_R has nothing to refill
                 _table_budget.log(f"timestep tables off for plan (B={B}, T={T}, {H}x{W}): {self.time_table_fallback}; "
                                   "+4 launches per step")
             else:

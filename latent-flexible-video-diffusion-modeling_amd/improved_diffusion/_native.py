@@ -146,6 +146,8 @@ _SIGS = {
     "lfvdm_renoise": ([c_fp] * 6 + [c_i, c_i, c_fp], c_i),
     "lfvdm_dyn_threshold_workspace": ([c_i, C.c_int64, C.POINTER(C.c_size_t)], c_i),
     "lfvdm_dyn_threshold": ([c_fp] * 5 + [c_i, c_i, c_fp, c_i, c_i, C.c_int64, C.c_double, C.c_float] + [c_fp] * 4, c_i),
+    "lfvdm_cfg_workspace": ([c_i, C.c_int64, C.POINTER(C.c_size_t)], c_i),
+    "lfvdm_cfg_combine": ([c_fp] * 5 + [c_i, c_i, c_fp, C.c_float, C.c_float] + [c_fp] * 3 + [c_i, c_i, C.c_int64, c_fp], c_i),
     "lfvdm_noise_prior_factor": ([c_fp, C.c_double, C.c_double, C.c_double, c_fp, c_i, c_i, c_fp], c_i),
     "lfvdm_noise_prior_fill": ([c_fp] * 5 + [c_i, c_i, C.c_int64, c_fp], c_i),
     "lfvdm_masked_mse_bwd": ([c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp], c_i),
@@ -798,6 +800,29 @@ def dyn_threshold(x, out, t, recip, recipm1, mean_type, x0hat_fma, frame_mask, p
                                     int(bool(x0hat_fma)), ptr(frame_mask), B, T, x.numel() // (B * T), float(percentile),
                                     float("inf") if max_value is None else float(max_value), ptr(xhat), ptr(stats),
                                     ptr(workspace, torch.uint8), stream()), "lfvdm_dyn_threshold")
+
+
+def cfg_workspace(B, inner):
+    """Bytes of workspace ``cfg_combine`` needs with rescale > 0 for B rows of ``inner`` elements (lfvdm_cfg_workspace).  It
+    is never zero-filled: a call writes every word it reads."""
+    n = C.c_size_t(0)
+    check(lib().lfvdm_cfg_workspace(int(B), int(inner), C.byref(n)), "lfvdm_cfg_workspace")
+    return int(n.value)
+
+
+def cfg_combine(x, out2, t, recip, recipm1, mean_type, x0hat_fma, frame_mask, scale, rescale, xhat, stats, workspace=None):
+    """Classifier-free guidance (lfvdm_cfg_combine): x / xhat (B, T, ...), ``out2`` (2B, T, ...) - rows [0, B) the conditional
+    network output, rows [B, 2B) the one with obs_mask = 0 -, ``frame_mask`` (B, T) or None, ``stats`` (B, 3) receives
+    (s_c, s_g, f).  ``x0hat_fma`` as in ``dyn_threshold``.  ``workspace`` (``cfg_workspace`` bytes) is needed with rescale > 0
+    only.  ``xhat`` is then the ``out`` of ``dyn_threshold`` or of an update entry under MEAN_X0."""
+    B, T = x.shape[0], x.shape[1]
+    if out2.shape[0] != 2 * B or out2.shape[1:] != x.shape[1:] or xhat.shape != x.shape or stats.numel() != 3 * B or (
+            frame_mask is not None and frame_mask.numel() != B * T):
+        raise RuntimeError("cfg_combine: out2 is (2B, T, ...) for x (B, T, ...), xhat is shaped like x, frame_mask is (B, T), "
+                           "stats is (B, 3)")
+    check(lib().lfvdm_cfg_combine(ptr(x), ptr(out2), ptr(t, torch.int64), ptr(recip), ptr(recipm1), int(mean_type),
+                                  int(bool(x0hat_fma)), ptr(frame_mask), float(scale), float(rescale), ptr(xhat), ptr(stats),
+                                  ptr(workspace, torch.uint8), B, T, x.numel() // (B * T), stream()), "lfvdm_cfg_combine")
 
 
 def noise_prior_factor(frame_indices, a, c, rho, out=None):

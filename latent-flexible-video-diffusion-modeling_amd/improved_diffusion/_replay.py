@@ -12,9 +12,12 @@ class ReplayedStep:
     table build, the warm-up and capture of ``_step_body`` (the subclass's), the chain-timeout check and the fall-back,
     and ``step``: a single replay."""
 
-    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise, time_tables=True):
+    def __init__(self, diffusion, unet, shape, clip_denoised, inject_noise, time_tables=True, plan_rows=1):
         # time_tables=False: a plan WITHOUT timestep tables (the embedding and RPE launches stay in the step) - for a step whose
         # frame indices change from one replay to the next, where a table keyed by this chain's frames would be rebuilt every time
+        # plan_rows = 2 (a sampler under classifier-free guidance): the private plan runs batch 2B - the window as given and,
+        # in rows [B, 2B), the same window without its observed frames; ``clock`` is the plan's step counter (2B rows), and
+        # ``t_buf``, like every B-sized buffer of the step, addresses rows [0, B) - a contiguous leading slice
         # inject_noise (parity tests): the replayed step READS ``self.noise`` - the caller fills it before every
         # ``step`` - instead of drawing it (the reference's th.randn_like, gaussian_diffusion.py:396)
         self.diffusion, self.unet, self.shape = diffusion, unet, tuple(shape)
@@ -31,12 +34,13 @@ class ReplayedStep:
         self.engine = unet.native_engine()
         # the chain walks a known schedule: everything that depends on (t, frame_indices) alone is tabulated once per
         # chain (Plan.build_time_tables / build_R_tables) instead of being recomputed by four launches in every step
-        self.plan = Plan(self.engine, B, T, H, W, False, time_steps=diffusion.num_timesteps if time_tables else None)
+        self.plan = Plan(self.engine, plan_rows * B, T, H, W, False, time_steps=diffusion.num_timesteps if time_tables else None)
         self.plan.refresh_weights()
         dev = self.plan.dev
         self.tb = diffusion.tables(dev)
         self.ts_table = diffusion.model_timestep_table(dev)
-        self.t_buf = self.plan.t_sel if self.plan.time_steps else th.zeros(B, dtype=th.int64, device=dev)
+        self.clock = self.plan.t_sel if self.plan.time_steps else th.zeros(self.plan.B, dtype=th.int64, device=dev)
+        self.t_buf = self.clock if plan_rows == 1 else self.clock[:B]
         self._table_events = None      # (start, end) events around the table build of the last begin()
         self._ts_key = tuple(self.ts_table.tolist())
         self.graph = None
@@ -68,8 +72,8 @@ class ReplayedStep:
         pl.ensure_R(n - 1)                               # (rolling window: the block the chain starts in)
         e1.record()
         self._table_events = (e0, e1)        # read lazily (table_build_ms): no host stall between windows / chains
-        self.t_buf.fill_(n)
-        pl.tick(self.t_buf, self.ts_table)
+        self.clock.fill_(n)
+        pl.tick(self.clock, self.ts_table)
 
     def _capture_step(self):
         """Tune the plan (once), warm ``_step_body`` up on a side stream and capture it as ``self.graph``.  The plan's
@@ -85,7 +89,7 @@ class ReplayedStep:
             pl.x_in.copy_(saved0)
         # warm-up on a side stream (sets kernel attributes, fills caches), then capture
         saved = pl.x_in.clone()
-        self.t_buf.fill_(self.diffusion.num_timesteps)
+        self.clock.fill_(self.diffusion.num_timesteps)
         s = th.cuda.Stream()
         s.wait_stream(th.cuda.current_stream())
         with th.cuda.stream(s):
@@ -111,7 +115,7 @@ class ReplayedStep:
             self._build_chain_tables(model_kwargs["frame_indices"])
             if self.graph is None:
                 self._capture_step()
-            self.t_buf.fill_(self.diffusion.num_timesteps)     # the step pre-decrements
+            self.clock.fill_(self.diffusion.num_timesteps)     # the step pre-decrements
         self.expected_t = self.diffusion.num_timesteps - 1
 
     def chain_timed_out(self):
@@ -132,7 +136,7 @@ class ReplayedStep:
 
     def step(self, i):
         if i != self.expected_t:  # arbitrary order requested: reset the device-side counter
-            self.t_buf.fill_(i + 1)
+            self.clock.fill_(i + 1)
         self.plan.ensure_R(i)
         self.graph.replay()
         self._abort_unchecked = True
@@ -149,8 +153,16 @@ class GraphSampler(ReplayedStep):
         self.rule = tuple(rule)
         if self.rule[0] not in ("ancestral", "ddim", "dpmpp2m") or len(self.rule) != (2 if self.rule[0] == "ddim" else 1):
             raise ValueError(f"unknown update rule {rule!r}")
-        super().__init__(diffusion, unet, shape, clip_denoised, inject_noise)
+        # classifier-free guidance (GaussianDiffusion.set_guidance), read ONCE here - it closes both sampler cache keys: the
+        # plan is built for batch 2B, begin() hands it cat[x, x] with obs_mask = 0 in the second half, the captured step
+        # combines the two halves of ``plan.out`` into ``xhat`` (lfvdm_cfg_combine), updates rows [0, B) as for an x0 model
+        # and mirrors them into rows [B, 2B)
+        self.guidance = diffusion.guidance
+        super().__init__(diffusion, unet, shape, clip_denoised, inject_noise, plan_rows=1 if self.guidance is None else 2)
         dev = self.plan.dev
+        B = self.shape[0]
+        # the state, the network output of the window as given: the plan's buffers, or with guidance their rows [0, B)
+        self.x_rows = self.plan.x_in if self.guidance is None else self.plan.x_in[:B]
         # device tables k1 / k2 / sigma of the DDIM rule (sigma None: deterministic) or k1 / k2 / k3 of the multistep rule,
         # and what the update is launched with
         self.multistep = self.rule[0] == "dpmpp2m"
@@ -165,13 +177,19 @@ class GraphSampler(ReplayedStep):
         # (B, T), which begin() uploads - and the update consumes ``xhat`` with the tuple of an x0-prediction model
         self.threshold = diffusion._threshold(self.clip)
         self.xhat = self.dyn_stats = self.dyn_ws = self.frame_mask = self.update_xhat = None
-        if self.threshold is not None:
+        self.cfg_stats = self.cfg_ws = None
+        if self.threshold is not None or self.guidance is not None:
             B, T = self.shape[:2]
             self.update_xhat = diffusion._update_args(dev, self.rule, as_xstart=True)
             self.xhat = th.empty(self.shape, device=dev)
+            self.frame_mask = th.ones(B, T, device=dev)
+        if self.threshold is not None:
             self.dyn_stats = th.zeros(B, 3, device=dev)
             self.dyn_ws = th.zeros(nat.dyn_threshold_workspace(B, self.xhat[0].numel()), dtype=th.uint8, device=dev)
-            self.frame_mask = th.ones(B, T, device=dev)
+        if self.guidance is not None:
+            self.cfg_stats = th.zeros(B, 3, device=dev)
+            if self.guidance[1] > 0.0:
+                self.cfg_ws = th.empty(nat.cfg_workspace(B, self.xhat[0].numel()), dtype=th.uint8, device=dev)
         # temporally correlated noise prior (GaussianDiffusion.set_noise_prior), read ONCE here like the threshold - it is
         # part of the sampler cache key.  begin() uploads the window's frame indices and factors their covariance once per
         # chain, outside the graph (lfvdm_noise_prior_factor); the captured step of a stochastic rule then draws L xi into
@@ -220,16 +238,27 @@ class GraphSampler(ReplayedStep):
         (``t_buf`` still holds the timestep the step consumed)."""
         self._denoise_body()
         if self.known is not None:
-            nat.known_blend(self.plan.x_in, self.known, self.known_mask, self.t_buf, self.known_tb["a"], self.known_tb["s"],
+            nat.known_blend(self.x_rows, self.known, self.known_mask, self.t_buf, self.known_tb["a"], self.known_tb["s"],
                             eps=self.known_eps, seed=self.seed, noise_out=self.known_noise)
             self.extra_launches += 1
+        self._mirror()
+
+    def _mirror(self, in_step=True):
+        """Under guidance: the new state of rows [0, B) -> rows [B, 2B) of the plan's input (one device copy, captured with
+        the step): both evaluations of the next step see the same x_t.  ``in_step`` False: the eager copy behind ``renoise``,
+        which is no launch of the step and is not counted."""
+        if self.guidance is not None:
+            B = self.shape[0]
+            self.plan.x_in[B:].copy_(self.x_rows)
+            self.extra_launches += int(in_step)
 
     def renoise(self):
         """Resampling: the state one forward step back up, to the level of the timestep the last step consumed (the clock
         still holds it), with fresh noise under the chain's seed (lfvdm_renoise: a Philox stream of its own).  One eager
         launch between replays; the next ``step`` of the same timestep puts the clock back."""
         tb = self.known_tb
-        nat.renoise(self.plan.x_in, self.t_buf, tb["sqrt_1mbeta"], tb["sqrt_beta"], self.seed)
+        nat.renoise(self.x_rows, self.t_buf, tb["sqrt_1mbeta"], tb["sqrt_beta"], self.seed)
+        self._mirror(in_step=False)
 
     def _denoise_body(self):
         """The clock and the forward, then at most one update launch, chosen by where the noise comes from."""
@@ -244,35 +273,44 @@ class GraphSampler(ReplayedStep):
         # under dynamic thresholding the head conv is never fused with the update (the branch of LFVDM_FUSED_HEAD=0, whatever
         # the environment says): the quantile needs the whole x0-hat before any element can be updated
         dyn = self.threshold is not None
+        cfg = self.guidance is not None      # nor under guidance: the update needs both halves of the network output
         # a noise prior takes the same branch where the step draws noise at all: L xi needs its own launch, which writes
         # ``noise`` for lfvdm_update_x0.  The deterministic rules launch nothing extra (only x_T carries the prior), and noise
         # the caller injects is used as given
         prior = self.prior is not None and not det and not self.inject_noise
-        fused = (not dyn and not prior and os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
+        fused = (not dyn and not cfg and not prior and os.environ.get("LFVDM_FUSED_HEAD", "1") != "0" and (in_kernel or self.inject_noise)
                  and pl.fuse_head_update(self.t_buf, self.tb, self.clip, self.seed, self.noise, self.pred, self.inject_noise,
                                          ddim=self.ddim, predict_xstart=self.x0_mode))
         # device-side clock: t <- max(t - 1, 0), model timestep <- table[t]  (t_buf holds "previous t"); with timestep
         # tables it also fetches the FiLM rows of the new t, and rides in the first launch of the forward
         tick_in_conv = bool(pl.time_steps) and os.environ.get("LFVDM_TICK_IN_CONV", "1") != "0"
         if tick_in_conv:
-            pl.launch(tick=(self.t_buf, self.ts_table))
+            pl.launch(tick=(self.clock, self.ts_table))
         else:
-            pl.tick(self.t_buf, self.ts_table)
+            pl.tick(self.clock, self.ts_table)
             pl.launch()
         draw = not (fused or in_kernel or self.inject_noise)
         # launches of a step beside the plan's own (bench.py reports launches per step): the clock, the update, the draw
         # (+ the four launches of the dynamic threshold, + the fill of the noise prior)
-        self.extra_launches = int(not tick_in_conv) + int(not fused) + int(draw) + (4 if dyn else 0) + int(prior)
+        # (+ the one or two launches of the guidance combine; the mirror copy is counted where it is issued)
+        self.extra_launches = (int(not tick_in_conv) + int(not fused) + int(draw) + (4 if dyn else 0) + int(prior)
+                               + ((2 if self.guidance[1] > 0.0 else 1) if cfg else 0))
         if fused:
             return
-        out, clip = pl.out, self.clip
+        out, clip, x_in = pl.out, self.clip, self.x_rows
+        fma = self.diffusion._x0hat_fma(self.update)
+        if cfg:      # both halves of the network output -> the guided x0-hat; from here on an x0 model's output
+            nat.cfg_combine(x_in, pl.out, self.t_buf, recip, recipm1, mean_type, fma, self.frame_mask, self.guidance[0],
+                            self.guidance[1], self.xhat, self.cfg_stats, self.cfg_ws)
+            recip, recipm1, c1, c2, sg, rule, mean_type = self.update_xhat
+            out = self.xhat
         if dyn:      # x0-hat of this model's mean type -> xhat, thresholded; the update then sees an x0 model's output
-            nat.dyn_threshold(pl.x_in, pl.out, self.t_buf, recip, recipm1, mean_type, self.diffusion._x0hat_fma(self.update),
+            nat.dyn_threshold(x_in, out, self.t_buf, recip, recipm1, mean_type, fma,
                               self.frame_mask, self.threshold[0], self.threshold[1], self.xhat, self.dyn_stats, self.dyn_ws)
             recip, recipm1, c1, c2, sg, rule, mean_type = self.update_xhat
             out, clip = self.xhat, False
         if self.multistep:
-            nat.update_ms_x0(pl.x_in, out, self.pred, self.t_buf, recip, recipm1, c1, c2, sg, mean_type, clip, pl.x_in,
+            nat.update_ms_x0(x_in, out, self.pred, self.t_buf, recip, recipm1, c1, c2, sg, mean_type, clip, x_in,
                              self.pred)
             return
         if prior:
@@ -281,16 +319,16 @@ class GraphSampler(ReplayedStep):
                 nat.noise_prior_fill(self.prior_L, self.noise, xi=self.noise)
             else:         # xi drawn in the kernel: the chain's key, this step's timesteps, a Philox stream of its own
                 nat.noise_prior_fill(self.prior_L, self.noise, seed=self.seed, t=self.t_buf)
-            nat.update_x0(pl.x_in, out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, clip, pl.x_in,
+            nat.update_x0(x_in, out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, clip, x_in,
                           self.pred)
             return
         if in_kernel:
-            nat.update_rng_x0(pl.x_in, out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
-                              mean_type, clip, pl.x_in, None if det else self.seed, self.pred)
+            nat.update_rng_x0(x_in, out, None if det else self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule,
+                              mean_type, clip, x_in, None if det else self.seed, self.pred)
             return
         if draw:
             self.noise.normal_()
-        nat.update_x0(pl.x_in, out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, clip, pl.x_in,
+        nat.update_x0(x_in, out, self.noise, self.t_buf, recip, recipm1, c1, c2, sg, rule, mean_type, clip, x_in,
                       self.pred)
 
     def begin(self, img, model_kwargs, known=None, known_mask=None, known_eps=None):
@@ -315,6 +353,9 @@ class GraphSampler(ReplayedStep):
         if self.prior is not None:           # this window's factor L, once per chain and before the (first chain's) capture
             self.prior_frames.copy_(model_kwargs["frame_indices"].reshape(self.prior_frames.shape))
             nat.noise_prior_factor(self.prior_frames, *self.prior, out=self.prior_L)
+        if self.guidance is not None:        # the doubled batch: cat[x, x], obs_mask = 0 in the second half
+            img = th.cat([img, img], dim=0)
+            model_kwargs = self.diffusion._doubled_kwargs(model_kwargs, self.shape[0])
         self._begin_chain(img, model_kwargs)
         self.seed.random_()                                 # this chain's noise key (torch's generator: seedable)
         if self.multistep:
@@ -342,7 +383,7 @@ class GraphSampler(ReplayedStep):
         return e0.elapsed_time(e1)
 
     def _state(self):
-        return {"sample": self.plan.x_in, "pred_xstart": self.pred, "attn": None}
+        return {"sample": self.x_rows, "pred_xstart": self.pred, "attn": None}
 
     def _check_order(self, i):
         """A multistep chain walks consecutive timesteps (its history is the step before); n - 1 starts a chain over."""
@@ -362,7 +403,7 @@ class GraphSampler(ReplayedStep):
             raise ValueError("inject_noise: the caller provides the noise of every step - use step()")
         self._check_order(i)
         if i != self.expected_t:
-            self.t_buf.fill_(i + 1)
+            self.clock.fill_(i + 1)
         left, t = int(n), int(i)
         if self.K > 1 and left >= self.K:
             if self.graph_k is None:

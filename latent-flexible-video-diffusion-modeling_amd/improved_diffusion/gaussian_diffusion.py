@@ -44,7 +44,12 @@ What is native here
     defined on a window's frame indices - not in the reference): noise = L xi with L the Cholesky factor of the per-sample
     frame covariance (csrc/noise_prior.hip: the factor once per chain, one fill launch in front of the un-fused update of
     a stochastic replayed step), for training noise, x_T and the per-step draws.  Off by default; its effect on sample
-    quality has not been measured.
+    quality has not been measured;
+  * classifier-free guidance on the observed frames (``set_guidance``, ``guidance_reference``; Ho & Salimans 2022 with the
+    rescale of Lin et al. 2024 - not in the reference) in every sampler: one forward on the doubled batch (the window as
+    given, and with ``obs_mask = 0``), one HIP launch (csrc/guidance.hip; two with a rescale) that writes the guided x0-hat,
+    then the threshold, if set, and the step's usual update as for an x0-prediction model.  Off by default; its effect on
+    sample quality has not been measured.
 
 Out of scope (not reached by the default CLIs): learned sigma (``learn_sigma=True``, also together with
 ``use_kl``: the reference's own 5-D code path asserts on it, so there is no behaviour to match),
@@ -198,6 +203,76 @@ def dynamic_threshold_reference(pred_xstart, latent_mask, percentile, max_value,
     return (out, s) if return_scale else out
 
 
+def parse_guidance(spec):
+    """"2" or "2:0.7" (scale[:rescale]) -> the keyword arguments of ``GaussianDiffusion.set_guidance`` (what LFVDM_GUIDANCE
+    holds); "" and "none": guidance off.  Only the shape of the string is judged here - the setter validates the values.
+    ValueError otherwise."""
+    if not isinstance(spec, str):
+        raise ValueError(f"guidance must be a string such as '2' or '2:0.7', got {spec!r}")
+    parts = [s.strip() for s in spec.strip().split(":")]
+    if parts in ([""], ["none"]):
+        return {"scale": None, "rescale": 0.0}
+    if len(parts) > 2:
+        raise ValueError(f"guidance {spec!r}: 'scale' or 'scale:rescale'")
+    try:
+        vals = [float(p) for p in parts]
+    except ValueError:
+        raise ValueError(f"guidance {spec!r}: scale and rescale must be numbers") from None
+    return {"scale": vals[0], "rescale": vals[1] if len(vals) == 2 else 0.0}
+
+
+def guidance_reference(x, out2, t, scale, rescale=0.0, latent_mask=None, recip=None, recipm1=None, fma=False,
+                       return_stats=False, dtype=th.float64):
+    """Classifier-free guidance on the observed frames (Ho & Salimans 2022) with the rescale of Lin et al. 2024, section 3.4,
+    in plain torch, float64 inside, on any device: the semantics of lfvdm_cfg_combine (include/lfvdm_hip.h) and the yardstick
+    of its tests.  ``x`` (B, T, ...); ``out2`` (2B, T, ...): rows [0, B) the network output o_c for the window as given, rows
+    [B, 2B) the output o_u for the same ``x``, ``frame_indices`` and ``latent_mask`` with ``obs_mask = 0``; ``t`` (B,).
+
+      1. o_g = o_u + scale (o_c - o_u), as written;
+      2. x0-hat of o_g and of o_c: ``recip`` / ``recipm1`` (the sqrt_recip / sqrt_recipm1 tables, indexed by ``t``) given -
+         an epsilon model, recip[t] x - recipm1[t] o (``fma``: the first product and the difference rounded once, the
+         convention of ``GaussianDiffusion._x0hat_fma``; only a float32 ``dtype`` can tell) - None: an x0 model, o itself;
+      3. ``rescale`` = phi > 0: per sample, over the elements of the frames with ``latent_mask != 0`` (B * T values, or None
+         = all frames), the population standard deviations s_c of x0-hat(o_c) and s_g of x0-hat(o_g);
+         f = phi s_c / s_g + (1 - phi), and f = 1 when nothing is selected or s_g == 0;  phi = 0: (s_c, s_g, f) = (0, 0, 1);
+      4. x0-hat(o_g) f for every element, in the dtype of ``x``.
+
+    ``return_stats``: also (s_c, s_g, f) as (B, 3) in ``dtype``.  ``dtype``: what "inside" is - float32 gives the tests their
+    model of the kernel's own precision."""
+    B = x.shape[0]
+    if out2.shape[0] != 2 * B or tuple(out2.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"out2 is (2B, ...) for x {tuple(x.shape)}, got {tuple(out2.shape)}")
+    o_c, o_u = out2[:B].to(dtype), out2[B:].to(dtype)
+    o_g = o_u + float(scale) * (o_c - o_u)
+
+    def x0hat(o):
+        if recip is None:
+            return o
+        r, rm1 = _bshape(recip[t].to(dtype), x.dim()), _bshape(recipm1[t].to(dtype), x.dim())
+        if fma and dtype != th.float64:      # one rounding of r x - fl(rm1 o): through float64, where r x is exact
+            return (r.double() * x.double() - (rm1 * o).double()).to(dtype)
+        return r * x.to(dtype) - rm1 * o
+    h_g = x0hat(o_g)
+    stats = th.zeros(B, 3, dtype=dtype, device=x.device)
+    stats[:, 2] = 1.0
+    phi = float(rescale)
+    if phi > 0.0:
+        T = x.shape[1] if x.dim() > 1 else 1
+        h_c = x0hat(o_c)
+        keep = None if latent_mask is None else latent_mask.reshape(B, T) != 0
+        for b in range(B):
+            sel = (lambda v: v.reshape(T, -1) if keep is None else v.reshape(T, -1)[keep[b].to(v.device)])
+            vc, vg = sel(h_c[b]).reshape(-1), sel(h_g[b]).reshape(-1)
+            if vc.numel() == 0:
+                continue
+            s_c, s_g = vc.std(unbiased=False), vg.std(unbiased=False)
+            stats[b, 0], stats[b, 1] = s_c, s_g
+            if float(s_g) != 0.0:
+                stats[b, 2] = phi * s_c / s_g + (1.0 - phi)
+    out = (h_g * _bshape(stats[:, 2], x.dim())).to(x.dtype)
+    return (out, stats) if return_stats else out
+
+
 class GaussianDiffusion:
     """Training / sampling utilities (reference :101-181).  Same constructor and attributes."""
 
@@ -248,6 +323,9 @@ class GaussianDiffusion:
         self.last_threshold_stats = None
         self.set_dynamic_threshold()
         self._noise_prior = None       # (a, c, rho) of set_noise_prior, or None: independent noise, today's paths
+        self._guidance = None          # (scale, rescale) of set_guidance, or None: one conditional evaluation, today's paths
+        self._cfg_ws = {}              # (device, B, inner) -> the eager steps' rescale workspace
+        self.last_guidance_stats = None
         self.setup_enc_dec()
 
     # ------------------------------------------------------------------ tables on device
@@ -560,6 +638,109 @@ class GaussianDiffusion:
             raise NotImplementedError(f"{what} assumes independent noise; the noise prior {format_noise_prior(self._noise_prior)!r} "
                                       "is set (set_noise_prior(None) turns it off)")
 
+    # ------------------------------------------------------------------ classifier-free guidance (not in the reference)
+    def set_guidance(self, scale=None, rescale=0.0):
+        """Classifier-free guidance on the observed frames (Ho & Salimans 2022; as in Video Diffusion Models / Imagen Video)
+        in every sampler of this diffusion: each step evaluates the network on the window as given AND on the same window
+        with ``obs_mask = 0`` - its observed frames fall out of the attention mask and are composed like padding, a state the
+        training mask distribution contains - as ONE call on the doubled batch, and the step continues from
+        o_u + scale (o_c - o_u) (``guidance_reference``).  ``rescale`` = phi in [0, 1] (Lin et al. 2024, section 3.4): the
+        guided x0-hat is scaled per sample towards the standard deviation of the conditional one over the window's latent
+        frames.  ``scale=None`` (the default), or ``scale == 1`` with ``rescale == 0``: off - exactly the code path, sampler
+        cache entry, plan batch and graphs there always were.  Needs no retraining, but the model must have seen windows
+        without observed frames in training (the reference's mask sampler provides them).
+
+        Native: lfvdm_cfg_combine writes the guided x0-hat (one launch; two with a rescale), which goes to the dynamic
+        threshold, if one is set, and then to the step's usual update launch as the output of an x0-prediction model; the
+        replayed step runs over a private plan of batch 2B (the head conv is then not fused with the update) and mirrors the
+        new state into the second half.  A noise prior is independent of guidance and stays allowed.  Guidance is a
+        sampling device: ``training_losses``, ``_vb_terms_bpd`` / ``calc_bpd_loop[_subsampled]``, the schedule search and
+        ``ddim_reverse_sample`` describe the model's own conditional distribution and do not read the setting.  Its effect
+        on the sample quality of a trained model has not been measured.  ValueError: a negative or non-finite scale, a
+        rescale outside [0, 1]."""
+        def number(name, v):
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"guidance: {name} must be a number, got {v!r}") from None
+            if not math.isfinite(v):
+                raise ValueError(f"guidance: {name} must be finite, got {v!r}")
+            return v
+        phi = number("rescale", 0.0 if rescale is None else rescale)
+        if not (0.0 <= phi <= 1.0):
+            raise ValueError(f"guidance: 0 <= rescale <= 1, got {phi!r}")
+        if scale is None:
+            self._guidance = None
+            return
+        w = number("scale", scale)
+        if w < 0.0:
+            raise ValueError(f"guidance: scale >= 0, got {w!r}")
+        self._guidance = None if (w == 1.0 and phi == 0.0) else (w, phi)
+
+    @property
+    def guidance(self):
+        """(scale, rescale) in force, or None: one conditional evaluation per step."""
+        return self._guidance
+
+    @staticmethod
+    def _doubled_kwargs(model_kwargs, B):
+        """The ``model_kwargs`` of the doubled batch: every tensor with B rows twice, ``obs_mask`` zero in the second half
+        (the unconditional window: same ``x``, ``frame_indices`` and ``latent_mask``; ``x0`` is not read where nothing is
+        observed)."""
+        if "obs_mask" not in model_kwargs:
+            raise ValueError("guidance is set (set_guidance): model_kwargs['obs_mask'] is needed - the unconditional "
+                             "evaluation is the window with obs_mask = 0")
+        obs = model_kwargs["obs_mask"]
+        if not th.is_tensor(obs) or obs.dim() == 0 or obs.shape[0] not in (1, B):
+            raise ValueError(f"guidance: obs_mask has one row per sample (B = {B}) or one row for all, got "
+                             f"{tuple(obs.shape) if th.is_tensor(obs) else obs!r}")
+        if obs.shape[0] != B:      # a broadcast mask: B rows first, or its second half would stay conditional
+            model_kwargs = dict(model_kwargs, obs_mask=obs.expand(B, *obs.shape[1:]))
+        kw = {}
+        for k, v in model_kwargs.items():
+            if th.is_tensor(v) and v.dim() > 0 and v.shape[0] == B:
+                kw[k] = th.cat([v, th.zeros_like(v) if k == "obs_mask" else v], dim=0)
+            else:
+                kw[k] = v
+        return kw
+
+    def _model_output(self, model, x, t, model_kwargs, return_attn_weights=False):
+        """What the per-step methods evaluate: (network output, attn) of ONE model call - on the window as given, or under
+        ``set_guidance`` on the doubled batch ``cat[x, x]`` (``_doubled_kwargs``), whose (2B, ...) output ``_update`` /
+        ``_update_denoised`` then combine (``guided=True``)."""
+        if self._guidance is None:
+            return model(x, self._scale_timesteps(t), return_attn_weights=return_attn_weights, **model_kwargs)
+        B = x.shape[0]
+        return model(th.cat([x, x], dim=0), self._scale_timesteps(th.cat([t, t], dim=0)),
+                     return_attn_weights=return_attn_weights, **self._doubled_kwargs(model_kwargs, B))
+
+    def _guide(self, x, out2, t, update, latent_mask):
+        """The (2B, ...) output of the doubled batch -> the guided x0-hat (B, ...): lfvdm_cfg_combine on the device,
+        ``guidance_reference`` for CPU tensors; (s_c, s_g, f) per sample stay in ``last_guidance_stats``.  ``update``: the
+        ``_update_args`` tuple of the step's rule and of this model's own mean type."""
+        w, phi = self._guidance
+        recip, recipm1, _, _, _, _, M = update
+        fma = self._x0hat_fma(update)
+        if not x.is_cuda or x.dtype != th.float32:      # CPU tensors, and the float64 yardstick of the tests
+            xhat, stats = guidance_reference(x, out2, t, w, phi, latent_mask, recip, recipm1, fma, return_stats=True)
+            self.last_guidance_stats = stats.to(x.dtype)
+            return xhat
+        B = x.shape[0]
+        ws = None
+        if phi > 0.0:
+            key = (str(x.device), B, x.numel() // B)
+            ws = self._cfg_ws.get(key)
+            if ws is None:
+                while len(self._cfg_ws) >= 4:
+                    self._cfg_ws.pop(next(iter(self._cfg_ws)))
+                ws = self._cfg_ws[key] = th.empty(nat.cfg_workspace(B, x.numel() // B), dtype=th.uint8, device=x.device)
+        xhat = th.empty_like(x, memory_format=th.contiguous_format)
+        stats = th.empty(B, 3, device=x.device)
+        nat.cfg_combine(x.contiguous(), out2.contiguous(), t.to(th.int64).contiguous(), recip, recipm1, M, fma,
+                        self._frame_mask(latent_mask, x), w, phi, xhat, stats, ws)
+        self.last_guidance_stats = stats
+        return xhat
+
     def _gather(self, name, t, ndim):
         return _bshape(self.tables(t.device)[name][t], ndim)
 
@@ -667,18 +848,26 @@ class GaussianDiffusion:
 
     # ``out`` below is the network's output: the noise, or x0-hat when ``predicts_xstart``
     def _update(self, x, out, t, noise, clip_denoised, rule=("ancestral",), reverse=False, want_mean=False, hist=None,
-                latent_mask=None):
+                latent_mask=None, guided=False):
         """One fused launch (lfvdm_update_x0) -> sample, x0-hat, and the mean on request.  ``noise`` None: the noise-free
         call of ``p_mean_variance`` (the ancestral kernel wants a pointer: ``x`` stands in); a deterministic DDIM rule
         reads no noise at all.  The multistep rule (lfvdm_update_ms_x0) reads ``hist``, the x0-hat of the step before
         (None: a first-order step), and no noise either.  Under ``set_dynamic_threshold`` (and ``clip_denoised``) the
         threshold launches come first (``latent_mask``: the window's latent frames, None = all) and the same update then
-        runs on their result with the tuple of an x0-prediction model and the clamp off."""
+        runs on their result with the tuple of an x0-prediction model and the clamp off.  ``guided`` (``set_guidance``):
+        ``out`` is the (2B, ...) output of the doubled batch; lfvdm_cfg_combine turns it into the guided x0-hat first, and
+        everything behind it - the threshold in its MEAN_X0 mode, the update - sees an x0-prediction model's output.  CPU
+        tensors under guidance take the plain-torch composition of ``_update_denoised``."""
+        if guided:
+            if not x.is_cuda:
+                return self._update_denoised(x, out, t, noise, clip_denoised, None, rule, reverse, hist, latent_mask, guided=True)
+            out = self._guide(x, out, t, self._update_args(x.device, rule, reverse), latent_mask)
         thr = self._threshold(clip_denoised)
         if thr is not None:
-            out = self._dyn_threshold_eager(x, out, t, self._update_args(x.device, rule, reverse), thr, latent_mask)
+            out = self._dyn_threshold_eager(x, out, t, self._update_args(x.device, rule, reverse, as_xstart=guided), thr,
+                                            latent_mask)
             clip_denoised = False
-        recip, recipm1, c1, c2, sg, R, M = self._update_args(x.device, rule, reverse, as_xstart=thr is not None)
+        recip, recipm1, c1, c2, sg, R, M = self._update_args(x.device, rule, reverse, as_xstart=guided or thr is not None)
         sample = th.empty_like(x, memory_format=th.contiguous_format)
         pred = th.empty_like(sample)
         if R == nat.RULE_DPMPP2M:
@@ -692,14 +881,20 @@ class GaussianDiffusion:
         return sample, pred, mean
 
     def _update_denoised(self, x, out, t, noise, clip_denoised, denoised_fn, rule=("ancestral",), reverse=False, hist=None,
-                         latent_mask=None):
+                         latent_mask=None, guided=False):
         """The same update with a user function applied to x0-hat before clipping (reference process_xstart,
         :305-309).  ``denoised_fn`` is arbitrary Python on a tensor, so this rarely used variant is composed of
         elementwise device ops around it instead of the fused kernel:  c1[t] * p0 + c2[t] * x + [t != 0] * sigma[t] * z,
         or, under the multistep rule, + k3[t] * (p0 - hist) in the noise's place.  Under ``set_dynamic_threshold`` the
-        clamp's place is taken by ``dynamic_threshold_reference`` over the frames of ``latent_mask``."""
+        clamp's place is taken by ``dynamic_threshold_reference`` over the frames of ``latent_mask``.  ``guided``: ``out``
+        is the (2B, ...) output of the doubled batch and x0-hat is the guided one (``_guide``); ``denoised_fn`` None: none."""
         n = x.dim()
-        pred = denoised_fn(self._xstart_from_output(x, t, out))
+        if guided:
+            pred = self._guide(x, out, t, self._update_args(x.device, rule, reverse), latent_mask)
+        else:
+            pred = self._xstart_from_output(x, t, out)
+        if denoised_fn is not None:
+            pred = denoised_fn(pred)
         thr = self._threshold(clip_denoised)
         if thr is not None:
             pred = dynamic_threshold_reference(pred, latent_mask, thr[0], thr[1])
@@ -725,13 +920,14 @@ class GaussianDiffusion:
         model_kwargs = model_kwargs or {}
         B = x.shape[0]
         assert t.shape == (B,)
-        eps, attn = model(x, self._scale_timesteps(t), return_attn_weights=return_attn_weights, **model_kwargs)
+        guided = self._guidance is not None
+        eps, attn = self._model_output(model, x, t, model_kwargs, return_attn_weights)
         if denoised_fn is not None:
             _, pred, mean = self._update_denoised(x, eps, t, None, clip_denoised, denoised_fn,
-                                                  latent_mask=model_kwargs.get("latent_mask"))
+                                                  latent_mask=model_kwargs.get("latent_mask"), guided=guided)
         else:   # noise-free update: the kernel returns the posterior mean and x0-hat in one pass
             _, pred, mean = self._update(x, eps, t, None, clip_denoised, want_mean=True,
-                                         latent_mask=model_kwargs.get("latent_mask"))
+                                         latent_mask=model_kwargs.get("latent_mask"), guided=guided)
         n = x.dim()
         return {"mean": mean, "variance": self._gather("model_variance", t, n).expand(x.shape),
                 "log_variance": self._gather("model_log_variance", t, n).expand(x.shape),
@@ -743,14 +939,16 @@ class GaussianDiffusion:
         the reference takes from ``th.randn_like`` so that trajectories can be compared across devices."""
         self._check_native_modes()
         model_kwargs = model_kwargs or {}
-        eps, attn = model(x, self._scale_timesteps(t), return_attn_weights=return_attn_weights, **model_kwargs)
+        guided = self._guidance is not None
+        eps, attn = self._model_output(model, x, t, model_kwargs, return_attn_weights)
         if noise is None:
             noise = self._prior_noise(th.randn_like(x), model_kwargs)
         if denoised_fn is not None:
             sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn,
-                                                    latent_mask=model_kwargs.get("latent_mask"))
+                                                    latent_mask=model_kwargs.get("latent_mask"), guided=guided)
         else:
-            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised, latent_mask=model_kwargs.get("latent_mask"))
+            sample, pred, _ = self._update(x, eps, t, noise, clip_denoised, latent_mask=model_kwargs.get("latent_mask"),
+                                           guided=guided)
         return {"sample": sample, "pred_xstart": pred, "attn": attn}
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
@@ -935,15 +1133,20 @@ class GaussianDiffusion:
         self._check_native_modes()
         model_kwargs = model_kwargs or {}
         assert t.shape == (x.shape[0],)
-        eps, _ = model(x, self._scale_timesteps(t), return_attn_weights=False, **model_kwargs)
+        # the reverse ODE (an encoding under the model's own conditional distribution) does not read set_guidance
+        guided = self._guidance is not None and not reverse
+        if guided:
+            eps, _ = self._model_output(model, x, t, model_kwargs)
+        else:
+            eps, _ = model(x, self._scale_timesteps(t), return_attn_weights=False, **model_kwargs)
         if float(eta) != 0.0 and noise is None:
             noise = self._prior_noise(th.randn_like(x), model_kwargs)
         if denoised_fn is not None:
             sample, pred, _ = self._update_denoised(x, eps, t, noise, clip_denoised, denoised_fn, ("ddim", eta), reverse,
-                                                    latent_mask=model_kwargs.get("latent_mask"))
+                                                    latent_mask=model_kwargs.get("latent_mask"), guided=guided)
         else:
             sample, pred, _ = self._update(x, eps, t, noise, clip_denoised, ("ddim", eta), reverse,
-                                           latent_mask=model_kwargs.get("latent_mask"))
+                                           latent_mask=model_kwargs.get("latent_mask"), guided=guided)
         return {"sample": sample, "pred_xstart": pred}
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, noise=None):
@@ -953,7 +1156,8 @@ class GaussianDiffusion:
         return self._ddim_step(model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, False, noise)
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
-        """x_{t+1} from the model using the DDIM reverse ODE (reference :573-610)."""
+        """x_{t+1} from the model using the DDIM reverse ODE (reference :573-610).  Does not read ``set_guidance``: it walks the
+        model's own conditional distribution."""
         assert eta == 0.0, "Reverse ODE only for deterministic path"
         return self._ddim_step(model, x, t, clip_denoised, denoised_fn, model_kwargs, 0.0, True)
 
@@ -982,13 +1186,15 @@ class GaussianDiffusion:
         self._check_native_modes()
         model_kwargs = model_kwargs or {}
         assert t.shape == (x.shape[0],)
-        out, _ = model(x, self._scale_timesteps(t), return_attn_weights=False, **model_kwargs)
+        guided = self._guidance is not None
+        out, _ = self._model_output(model, x, t, model_kwargs)
         if denoised_fn is not None:
             sample, pred, _ = self._update_denoised(x, out, t, None, clip_denoised, denoised_fn, ("dpmpp2m",),
-                                                    hist=prev_pred_xstart, latent_mask=model_kwargs.get("latent_mask"))
+                                                    hist=prev_pred_xstart, latent_mask=model_kwargs.get("latent_mask"),
+                                                    guided=guided)
         else:
             sample, pred, _ = self._update(x, out, t, None, clip_denoised, ("dpmpp2m",), hist=prev_pred_xstart,
-                                           latent_mask=model_kwargs.get("latent_mask"))
+                                           latent_mask=model_kwargs.get("latent_mask"), guided=guided)
         return {"sample": sample, "pred_xstart": pred}
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
@@ -1026,7 +1232,10 @@ class GaussianDiffusion:
         # the same shape never share a captured graph
         # and so is the dynamic threshold in force (last; None: the static clamp): the sampler reads it when it is built; and so
         # is the noise prior in force (in front of it; None: independent noise).  Known-region samplers never run under a prior
+        # and guidance in force goes behind both (set_guidance; the key WITHOUT guidance is the tuple it always was)
         key = (id(unet), shape, bool(clip_denoised), tuple(rule), self._noise_prior, self._threshold(clip_denoised))
+        if self._guidance is not None:
+            key += (self._guidance,)
         return self._cached_sampler(self._samplers, key, unet, shape, clip_denoised, rule)
 
     # ------------------------------------------------------------------ known-region sampling (RePaint; not in the reference)
@@ -1047,6 +1256,8 @@ class GaussianDiffusion:
         """``_graph_sampler`` for samplers whose captured step ends with the blend launch.  They live in a cache of their
         own: the plain samplers, their graphs and their launch counts are what they were."""
         key = (id(unet), shape, bool(clip_denoised), tuple(rule), "known", self._threshold(clip_denoised))
+        if self._guidance is not None:
+            key += (self._guidance,)
         return self._cached_sampler(self._known_samplers, key, unet, shape, clip_denoised, rule, known_fixed=bool(fixed_noise))
 
     @staticmethod
@@ -1158,7 +1369,9 @@ class GaussianDiffusion:
         num_timesteps for RESCALED_KL; the gradient reaches the network through ``_autograd._VbTerm``.
 
         ``set_loss_weighting`` other than "none" (MSE losses): 'loss' = w[t] * mse, a tensor of its own and the only
-        differentiable term; 'mse' and 'eval-mse' keep their unweighted values (one launch, ``_autograd._TrainLoss``)."""
+        differentiable term; 'mse' and 'eval-mse' keep their unweighted values (one launch, ``_autograd._TrainLoss``).
+
+        Does not read ``set_guidance``: the loss is that of the model's own conditional distribution."""
         self._check_native_modes()
         if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE, LossType.KL, LossType.RESCALED_KL):
             raise NotImplementedError(self.loss_type)
@@ -1237,7 +1450,8 @@ class GaussianDiffusion:
     def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None, latent_mask=None):
         """One term of the variational bound in bits per dimension (reference :687-720) -> {'output' (N,), 'pred_xstart'}:
         the decoder NLL at t == 0, KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t)) elsewhere.  One model call and one fused
-        launch (lfvdm_vb_terms); differentiable with respect to the model output for clip_denoised=False."""
+        launch (lfvdm_vb_terms); differentiable with respect to the model output for clip_denoised=False.  Does not read
+        ``set_guidance``: the bound is that of the model's own conditional distribution."""
         res = self._vb_terms(model, x_start, x_t, t, clip_denoised, model_kwargs, latent_mask, want_pred=True)
         return {"output": res["output"], "pred_xstart": res["pred_xstart"]}
 
@@ -1255,7 +1469,8 @@ class GaussianDiffusion:
         of timesteps, or a 2-D numpy array with one ROW of timesteps per batch element.
 
         The full descending walk of a native U-Net on the device with ``model_kwargs`` given replays one captured hipGraph
-        per step (``BpdEvaluator``); everything else runs one model call and one fused launch per step."""
+        per step (``BpdEvaluator``); everything else runs one model call and one fused launch per step.  Does not read
+        ``set_guidance`` (nor does ``calc_bpd_loop``): the bound is that of the model's own conditional distribution."""
         from .unet import UNetVideoModel
         self._refuse_noise_prior("the variational bound (calc_bpd_loop / calc_bpd_loop_subsampled)")
         B = x_start.shape[0]

@@ -41,7 +41,9 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     chain; in the reference ``--use_ddim`` only renames the results folder, here it selects the sampler), use_dpm_solver
     (DPM-Solver++(2M) instead; together with use_ddim: ValueError), dynamic_threshold / dynamic_threshold_max (a percentile
     and an optional cap: ``diffusion.set_dynamic_threshold`` is called with them before the first window; without the
-    attribute, LFVDM_DYNAMIC_THRESHOLD="0.995" or "0.995:1.5" is read; neither: the diffusion's setting stays), noise_prior (a spec
+    attribute, LFVDM_DYNAMIC_THRESHOLD="0.995" or "0.995:1.5" is read; neither: the diffusion's setting stays), guidance_scale / guidance_rescale
+    (classifier-free guidance on the observed frames: ``diffusion.set_guidance`` is called with them before the first window;
+    without guidance_scale, LFVDM_GUIDANCE="2" or "2:0.7" is read; neither: the diffusion's setting stays), noise_prior (a spec
     of ``noise_prior.parse_noise_prior`` for ``diffusion.set_noise_prior``, else LFVDM_NOISE_PRIOR, resolved the same way;
     ``trained_noise_prior``, the spec in the checkpoint's config, is compared with it and a difference is logged; a prior
     together with known_video: NotImplementedError), adaptive_metric (a spec of ``frame_select.parse_frame_metric``, "msl2:1" ..
@@ -69,6 +71,9 @@ def sample_video(args, model, diffusion, batch, just_get_indices=False, verbose=
     thr = resolve_dynamic_threshold(args)
     if thr is not None:      # before the first window: the samplers read the setting when they are built
         diffusion.set_dynamic_threshold(**thr)
+    cfg = resolve_guidance(args)
+    if cfg is not None:      # likewise
+        diffusion.set_guidance(**cfg)
     prior = resolve_noise_prior(args)
     if prior is not None:    # likewise; "none" turns a prior off, no setting at all leaves the diffusion object as it is
         diffusion.set_noise_prior(prior)
@@ -150,6 +155,21 @@ def resolve_dynamic_threshold(args):
     return None if spec is None else parse_dynamic_threshold(spec)
 
 
+def resolve_guidance(args):
+    """``args.guidance_scale`` (with ``args.guidance_rescale``) > LFVDM_GUIDANCE > None (leave the diffusion object as it is)
+    -> the keyword arguments of ``GaussianDiffusion.set_guidance``, or None."""
+    import os
+    from .gaussian_diffusion import parse_guidance
+    scale = getattr(args, "guidance_scale", None)
+    rescale = getattr(args, "guidance_rescale", None)
+    if scale is not None:
+        return {"scale": scale, "rescale": 0.0 if rescale is None else rescale}
+    if rescale is not None:
+        raise ValueError("guidance_rescale needs guidance_scale")
+    spec = os.environ.get("LFVDM_GUIDANCE")
+    return None if spec is None else parse_guidance(spec)
+
+
 def resolve_noise_prior(args):
     """``args.noise_prior`` > LFVDM_NOISE_PRIOR > None (leave the diffusion object as it is) -> the spec for
     ``GaussianDiffusion.set_noise_prior`` ("none" included: it turns a prior off), or None.  Malformed: ValueError."""
@@ -197,7 +217,7 @@ def default_sampling_args(**kw):
     """Namespace with the defaults of the reference CLI (video_sample.py:171-192) for programmatic use."""
     d = dict(sampling_scheme="autoreg", n_obs=36, max_frames=20, max_latent_frames=None, clip_denoised=True,
              optimality=None, eval_dir=None, use_ddim=False, ddim_eta=0.0, use_dpm_solver=False,
-             dynamic_threshold=None, dynamic_threshold_max=None, noise_prior=None, adaptive_metric=None,
+             dynamic_threshold=None, dynamic_threshold_max=None, guidance_scale=None, guidance_rescale=None, noise_prior=None, adaptive_metric=None,
              device="cuda" if th.cuda.is_available() else "cpu")
     d.update(kw)
     if d["use_ddim"] and d["use_dpm_solver"]:
